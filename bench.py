@@ -2,7 +2,7 @@
 """Headline benchmark: audio frames/s, waveform-on-device -> log-mel -> TDS encoder ->
 diarization head (128-d features + argmax speaker ids), BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W [--workload clip|segments|decode]
+    python bench.py --gpus N --steps K --warmup W [--workload clip|segments|decode] [--dump-outputs DIR]
 
 One process per GPU.  Typed as above with N > 1 and no WORLD_SIZE in the environment, the script starts its own N
 rank processes (127.0.0.1 rendezvous) before anything touches the GPU and prints rank 0's line; under
@@ -76,6 +76,9 @@ def parse():
     ap.add_argument("--cpu-threads", type=str, default="8,16,32,64,128", help="thread counts the CPU baseline is swept over")
     ap.add_argument("--passes", type=int, default=3, help="timed passes of --steps steps each; `value` is the MEDIAN pass (BASELINE.md section 3: median of >= 3 runs)")
     ap.add_argument("--no-clock-sampler", action="store_true", help="do not sample the shader clock / socket power during the timed passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last step of the timed passes returned as DIR/<name>.npy (float32 / float64, <= 64 MB "
+                         "in all: a fixed seeded sample of rows beyond that), for output-for-output comparison of two builds")
     a = ap.parse_args()
     if a.workload is None:
         a.workload = "clip" if a.gpus == 1 else "segments"
@@ -86,11 +89,27 @@ def parse():
     return a
 
 
+def build_native():
+    """__graft_entry__.build(), on a tree that may have been built beforehand by another user and be read-only to this one:
+    a build() that takes its lock file even when there is nothing to build raises PermissionError there.  The library is
+    then loaded as it is, if it is not older than any of its sources; otherwise the error stands."""
+    import glob
+    import __graft_entry__ as g
+    try:
+        g.build()
+    except PermissionError:
+        lib = os.path.join(ROOT, "tal_asrd_amd", "libtal_asrd_hip.so")
+        srcs = glob.glob(os.path.join(ROOT, "tal_asrd_amd", "csrc", "*")) + [os.path.join(ROOT, "include", "tal_asrd.h")]
+        if not os.path.exists(lib) or any(os.path.getmtime(s) > os.path.getmtime(lib) for s in srcs):
+            raise
+        from tal_asrd_amd import _native
+        _native.lib()
+
+
 def self_launch(args):
     """`python bench.py --gpus N` typed by hand: start the N rank processes (nothing in THIS process has touched the GPU;
     the library is built once here so that the ranks do not race hipcc)."""
-    import __graft_entry__ as g
-    g.build()
+    build_native()
     # this launcher serves the rendezvous store for the whole run, as torch.distributed.run's agent does (the ranks see
     # TORCHELASTIC_USE_AGENT_STORE and connect as clients): the RCCL probe, the agreement on its outcome and every process
     # group of the run hang off ONE store on ONE reserved port.  (A TCP store is host-side only: nothing here touches the GPU.)
@@ -287,10 +306,48 @@ def load_traffic():
                   "scripts/profile_round.sh" % (", ".join(stale) or "no profiles/rN_pmc_traffic.json"))
 
 
-def decode_episode_gpu(system, sdm, audio, lens, sync):
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: all files together, .npy headers included
+DUMP_SEED = 1234
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: {name: tensor | ndarray} -> outdir/<name>.npy.  Floating results are written as float32 (float64 stays
+    float64), integer ones (ids, tokens) as float64, which holds them exactly.  Arrays are written as rows: all but the last
+    dimension flattened, a 1-d array as a column (so ids [n * T] line up with features [n, T, E]).  If everything together
+    is over DUMP_BYTES, every array keeps the same fraction of its rows, picked by a generator seeded with DUMP_SEED: arrays
+    with the same row count keep the same rows (features and ids of one frame stay side by side), and the same shapes give
+    the same sample on every run.
+    -> {name: {"shape": shape written, "rows_of": row count before sampling}}."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu()
+            a = (a.float() if a.is_floating_point() and a.dtype != torch.float64 else a).numpy()
+        a = np.asarray(a)
+        a = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) and a.dtype != np.float64 else np.float64)
+        host[name] = a.reshape(-1, a.shape[-1]) if a.ndim >= 2 else a.reshape(-1, 1)
+    total = sum(a.nbytes for a in host.values())
+    budget = DUMP_BYTES - 1024 * len(host)
+    keep = min(1.0, budget / total) if total else 1.0
+    os.makedirs(outdir, exist_ok=True)
+    written = {}
+    for name, a in host.items():
+        n = a.shape[0]
+        if keep < 1.0:
+            k = max(1, int(n * keep))
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        written[name] = {"shape": list(a.shape), "rows_of": n}
+    return written
+
+
+def decode_episode_gpu(system, sdm, audio, lens, sync, outputs=None):
     """BASELINE.json configs[4] on one episode: ASR encode + sliding-window greedy decode (tal/asr/system.py:254-524,654-707)
     + SDModel pass (tal/baseline/reconcile.py:76-85) + word-level WDER-input pooling / voting
-    (tal/utils/aligned_to_wder_format.py:150-214).  -> stats dict (ms per leg)."""
+    (tal/utils/aligned_to_wder_format.py:150-214).  -> stats dict (ms per leg).  `outputs` (a dict) receives what the chain
+    hands its caller: the generated tokens, the SD features and ids, and the WDER-format words."""
     from tal_asrd_amd.wder_format import unaligned_to_wder
     sync()
     t0 = time.perf_counter()
@@ -303,6 +360,8 @@ def decode_episode_gpu(system, sdm, audio, lens, sync):
     ref = [{"episode": "e", "utterance": "x", "speaker": 0, "role": "host"}]
     out = unaligned_to_wder([(ref, kept)], {"e": feat[0]}, {"e": ids[0]}, {}, system.tokenizer, word_level=True, num_ids=6008)
     sync(); t3 = time.perf_counter()
+    if outputs is not None:
+        outputs.update(gen=gen, feat=feat, ids=ids, words=out[0][1])
     return dict(tokens=int(gen.shape[1]) - 1, utterances=len(utts), words=len(out[0][1]), decode_ms=1e3 * (t1 - t0),
                 sd_ms=1e3 * (t2 - t1), wder_format_ms=1e3 * (t3 - t2), total_ms=1e3 * (t3 - t0)), gen
 
@@ -469,8 +528,7 @@ def main():
         raise SystemExit(self_launch(args))
 
     import torch
-    import __graft_entry__ as g
-    g.build()
+    build_native()
     from tal_asrd_amd import _native, synth
     from tal_asrd_amd import distributed as D
 
@@ -543,10 +601,20 @@ def main():
         audio = torch.from_numpy(synth.synth_audio_batch(1, L, 2469 + rank)).to(dev)     # (generate_unaligned casts it to half, system.py:285)
         lens = torch.tensor([L])
         stats = {}
+        last = {}
 
         def step():
-            st, _ = decode_episode_gpu(system, sdm, audio, lens, sync)
+            st, _ = decode_episode_gpu(system, sdm, audio, lens, sync, outputs=last)
             stats.update(st)
+
+        def last_outputs():
+            words = last["words"]
+            emb = [w[1][0] for w in words]
+            return {"tokens": last["gen"].reshape(-1), "sd_feat": last["feat"].reshape(-1, last["feat"].shape[-1]),
+                    "sd_ids": last["ids"].reshape(-1),
+                    "word_embedding": torch.cat(emb) if emb else torch.zeros(0, last["feat"].shape[-1]),
+                    "word_embedding_rows": torch.tensor([e.shape[0] for e in emb], dtype=torch.int64),
+                    "word_speaker_id": torch.tensor([w[1][1] for w in words], dtype=torch.int64)}
         units_per_step = world * frames
         scaling = "weak"
         workload = ("1 x %.0f s 16 kHz episode per GPU: ASRModel encode + sliding-window greedy decode "
@@ -606,6 +674,11 @@ def main():
                     local = {i: v.to(gdev) for i, v in local.items()}
                 packed = plan.gather(local)
             gathered["packed"] = packed
+
+        def last_outputs():
+            # (rank 0's gathered [tp, 129] rows per segment, unpacked into what the reference call returns)
+            feat, ids = zip(*(D.unpack_feat_ids(p) for p in gathered["packed"]))
+            return {"feat": torch.cat(feat), "ids": torch.cat(ids)}
         units_per_step = n_seg * frames
         scaling = "strong"
         workload = ("%d x %.0f s 16 kHz segments = one reference call over a [%d, L] batch, sharded over %d GPU(s) by "
@@ -631,8 +704,11 @@ def main():
             gather_feat = [torch.empty(n_rows, f0.shape[-1], device=gdev) for _ in range(world)]
             gather_ids = [torch.empty(n_rows, dtype=torch.int32, device=gdev) for _ in range(world)]
 
+        last = {}
+
         def step():
             outs = [model.speaker_ids(clip) for clip in clips]
+            last["outs"] = outs
             if dist is not None:
                 feat = torch.cat([o[0].reshape(-1, o[0].shape[-1]) for o in outs])
                 ids = torch.cat([o[1].reshape(-1) for o in outs])
@@ -643,6 +719,13 @@ def main():
                 # pending gathers are waited for inside the timed region.
                 pending.append((dist.gather(feat, gather_feat if rank == 0 else None, dst=0, async_op=True),
                                 dist.gather(ids, gather_ids if rank == 0 else None, dst=0, async_op=True), feat, ids))
+
+        def last_outputs():
+            # (at N > 1, every rank's clips as gathered to rank 0, rank order)
+            if dist is not None:
+                return {"feat": torch.cat(gather_feat), "ids": torch.cat(gather_ids)}
+            return {"feat": torch.cat([o[0].reshape(-1, o[0].shape[-1]) for o in last["outs"]]),
+                    "ids": torch.cat([o[1].reshape(-1) for o in last["outs"]])}
         units_per_step = world * args.segments * frames
         scaling = "weak"
         workload = ((("%d x %.0f s 16 kHz clips per GPU as one batched call " if args.batched else
@@ -821,6 +904,10 @@ def main():
             extra["gpu_sclk_mhz"] = pass_clk[med]["sclk_mhz"]
             extra["gpu_power_w"] = pass_clk[med]["power_w"]
             extra["passes"]["clocks"] = pass_clk
+        if args.dump_outputs and rank == 0:
+            # the last step of the passes `value` comes from (the passes below run the step again, one of them on other kernels)
+            sync()
+            extra["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, last_outputs())}
         if prof and args.workload != "decode":
             elapsed_prof = timed_pass(True)
             extra["ms_per_step_with_launch_events"] = 1e3 * elapsed_prof / args.steps
