@@ -63,6 +63,8 @@ const char* tal_last_error(void);
  *                         measured SLOWER than the chain, profiles/r5_decode_persistent_step.txt -- kept as a measurement switch)
  *   decode_persist_wgs    workgroups per session of that launch (default 32)
  *   logmel_mfma           1: the log-mel front-end as the float64 matrix-core DFT instead of the fast transform (see tal_logmel_fwd)
+ *   logmel_general        1: the host mirror builds general plans (tal_logmel_general_*) for the default 16 kHz / 80 shape too
+ *                         (a comparison switch: the C calls themselves do not read it)
  *   gemm_s64_below        fp16x3 relu / residual layers run on 64 x 80 tiles without K slices while those tiles number
  *                         at most this many per CU (default 2; 0: never)
  *   gconv_short_below     grouped convs use 64-step tiles while the long tiles would give a CU fewer workgroups than
@@ -108,6 +110,27 @@ int tal_logmel_f16_fwd(const void* plan, const void* audio_f16, int B, int64_t L
                        void* workspace, size_t workspace_bytes, void* stream);
 /* x[i] -= *mean for n floats (second half of the two-step / multi-GPU form). */
 int tal_subtract_scalar(float* x, int64_t n, const float* mean, void* stream);
+
+/* General front-end: LogMelSpec(sr, n_mels) for any sample rate and mel count (csrc/logmel_general.hip).  Runtime shapes:
+ * n_fft 32..2048 (odd or even), hop 1..n_fft, n_mels 1..256; reflect-pad n_fft/2, one-sided DFT with n_fft/2 + 1 bins.  Same
+ * precision policy as tal_logmel_fwd (window x sample, DFT, power: float64; mel projection, log: float32).  The window [n_fft] and
+ * the filterbank [n_fft/2 + 1, n_mels] are taken as given (any values; a filter with empty support gives log(eps)).
+ * frames for L samples at hop: 1 + L / hop (0 for hop < 1). */
+int64_t tal_logmel_frames(int64_t L, int hop);
+/* bytes of a general plan; 0 outside the limits above. */
+size_t tal_logmel_general_plan_bytes(int n_fft, int n_mels);
+/* build the plan (device memory of tal_logmel_general_plan_bytes(n_fft, n_mels) bytes) from device buffers window [n_fft] and
+ * fb [n_fft/2 + 1, n_mels]; one-time, synchronises `stream`.  TAL_EINVAL with a message outside the limits. */
+int tal_logmel_general_plan_init(const float* window, int n_fft, int hop, const float* fb, int n_mels, void* plan, void* stream);
+size_t tal_logmel_general_workspace_bytes(int n_fft, int hop, int B, int64_t L);
+/* audio [B, L] (fp32, or fp16 when audio_is_f16: widened exactly, so the result equals the fp32 call on the widened waveform
+ * bit for bit) -> out [B, T, n_mels], T = torch.stft's frame count tal_logmel_frames(L - n_fft % 2, hop) (1 + L/hop for even
+ * n_fft); subtract_mean, mean_out and sum_out as tal_logmel_fwd.  n_fft / hop / n_mels are
+ * the plan's (the host keeps them; nothing is read back): a plan built for another shape makes the outputs NaN.  Needs
+ * L > n_fft/2 (reflect padding, as torch.stft).  Enqueues launches only: no allocation, no synchronisation. */
+int tal_logmel_general_fwd(const void* plan, int n_fft, int hop, int n_mels, const void* audio, int audio_is_f16, int B, int64_t L,
+                           float eps, int subtract_mean, float* out, float* mean_out, double* sum_out, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Dense layer: y = epilogue(x . W^T + b), nn.Linear / 1x1 Conv1d.

@@ -127,6 +127,7 @@ enum Option {
     OPT_GCONV_C1_FUSE,            // first resize conv computed inside the first TDSBlock conv's launch (round 6: bit-identical, no faster -- off)
     OPT_DECODE_FOLD_ROWS,         // the folded decoder layer is taken up to this many rows (prefix tokens) per problem (default 64)
     OPT_GCONV_LONG_TT,            // long inputs, 10- / 14-channel TDSBlock convs: 0 = 256- / 128-step tiles (default), 256 / 128 = that length for both
+    OPT_LOGMEL_GENERAL,           // the host mirror builds general log-mel plans (csrc/logmel_general.hip) for the default 16 kHz / 80 shape too
     OPT_COUNT
 };
 int opt(Option o);
@@ -237,6 +238,10 @@ int launch_gconv_s2_f16x3(const float* x, const void* w_frag, const float* bias,
 int launch_gconv_res_f16x3(const float* x, const void* w_frag, const float* bias, float alpha, int B, int64_t T, int C, int groups,
                            float* y, void* y_split, hipStream_t s, int* range_flag = nullptr, bool x_split = false);
 int launch_argmax_rows(const float* x, int64_t M, int N, int32_t* ids, hipStream_t s);
+// log-mel epilogue shared by both front-ends (csrc/logmel.hip): fixed-order reduction of `nparts` per-workgroup partial sums
+// -> {sum, count} (sum_out), the float mean (mean_out and mean_ws[0]), then x[0 .. n) -= mean if subtract_mean
+int launch_logmel_mean(const double* partial, int64_t nparts, double count, float* mean_out, double* sum_out, float* mean_ws,
+                       int subtract_mean, float* x, int64_t n, hipStream_t s, const char* what);
 // A-stationary speaker-logit arg-max (csrc/head.hip): partials [M, head_argmax_partials(M, S)] for argmax_partials_kernel
 bool head_argmax_applicable(int64_t M, int S, int E);
 int head_argmax_partials(int64_t M, int S);

@@ -611,6 +611,14 @@ static int launch_subtract(float* x, int64_t n, const float* mean, hipStream_t s
     return TAL_OK;
 }
 
+int launch_logmel_mean(const double* partial, int64_t nparts, double count, float* mean_out, double* sum_out, float* mean_ws,
+                       int subtract_mean, float* x, int64_t n, hipStream_t s, const char* what) {
+    hipLaunchKernelGGL(logmel_mean_kernel, dim3(1), dim3(256), 0, s, partial, nparts, count, mean_out, sum_out, mean_ws);
+    TAL_CHECK_LAUNCH(what);
+    if (subtract_mean) return launch_subtract(x, n, mean_ws, s);
+    return TAL_OK;
+}
+
 }  // namespace tal
 
 using namespace tal;

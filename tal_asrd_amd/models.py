@@ -126,9 +126,13 @@ class MelSpectrogram(nn.Module):
 
     def __init__(self, sample_rate, n_mels, n_fft, win_length, hop_length):
         super().__init__()
-        if (sample_rate, n_fft, win_length, hop_length, n_mels) != (16000, 400, 400, 160, 80):
-            raise N.NativeError("the HIP front-end is built for 16 kHz / 400 / 400 / 160 / 80 mels "
-                                "(tal/asr/models.py:24-32)")
+        if win_length != n_fft:
+            raise N.NativeError("MelSpectrogram: the HIP front-end takes win_length == n_fft (tal/asr/models.py:24-32), got %d and %d"
+                                % (win_length, n_fft))
+        err = ops.logmel_shape_error(n_fft, hop_length, n_mels)
+        if err:
+            raise N.NativeError("MelSpectrogram(sample_rate=%s): the HIP front-end limit is violated: %s" % (sample_rate, err))
+        self.hop_length = hop_length
         self.spectrogram = _Spectrogram(n_fft)
         self.mel_scale = _MelScale(n_mels, sample_rate, n_fft // 2 + 1)
 
@@ -148,7 +152,7 @@ class LogMelSpec(nn.Module):
         win, fb = self.mel_transform.spectrogram.window, self.mel_transform.mel_scale.fb
         key = (win.data_ptr(), win._version, fb.data_ptr(), fb._version)
         if self._plan is None or self._plan_key != key:
-            self._plan = ops.logmel_plan(win, fb)
+            self._plan = ops.logmel_plan(win, fb, hop=self.mel_transform.hop_length)
             self._plan_key = key
         return self._plan
 
@@ -404,12 +408,21 @@ def padding_mask(audio_lens, t_out, device):
     return mask.to(device)
 
 
+def _check_encoder_mels(n_mels, who):
+    """The encoder is sized from n_mels (tds_sizes = [n, 10 n, 14 n, 18 n], groups = n): its pointwise layers need C % 4 == 0,
+    which 10 * n_mels meets for even n_mels only."""
+    if (10 * n_mels) % 4 != 0:
+        raise N.NativeError("%s(n_mels=%d): the encoder's pointwise layers need C %% 4 == 0, and C = 10 * n_mels = %d is not "
+                            "(n_mels must be even)" % (who, n_mels, 10 * n_mels))
+
+
 class SDModel(nn.Module):
     """Separate-diarizer baseline (tal/asr/models.py:400-485)."""
 
     def __init__(self, num_speakers=6008, n_mels=80, dropout=0.2, embed_size=128):
         super().__init__()
         self.num_speakers = num_speakers
+        _check_encoder_mels(n_mels, "SDModel")
         tds_sizes = [n_mels, 10 * n_mels, 14 * n_mels, 18 * n_mels]
         tds_depths = [2, 3, 6]
         self.logmelspec = LogMelSpec(n_mels=n_mels)
@@ -576,6 +589,7 @@ class ASRModel(nn.Module):
         self.use_speaker_head = use_speaker_head
         self.model_type = model_type
         self.n_head = n_head
+        _check_encoder_mels(n_mels, "ASRModel")
         tds_sizes = [n_mels, 10 * n_mels, 14 * n_mels, 18 * n_mels]
         tds_depths = [2, 3, 6]
         if model_type == "1x":

@@ -22,14 +22,50 @@ def _f32c(t, what):
 
 
 # ------------------------------------------------------------------ log-mel
-def logmel_plan(window, fb):
-    """Device plan (Hann-folded DFT basis + sparse mel filters) for tal_logmel_fwd."""
+NFFT_MIN, NFFT_MAX, NMELS_MAX = 32, 2048, 256     # limits of the general front-end (csrc/logmel_general.hip)
+
+
+class LogmelGeneralPlan:
+    """Device plan of the general front-end (tal_logmel_general_*) with the shape it was built for, kept on the host so that a
+    call never reads device memory to size its output."""
+
+    def __init__(self, buf, n_fft, hop, n_mels):
+        self.buf, self.n_fft, self.hop, self.n_mels = buf, n_fft, hop, n_mels
+
+    @property
+    def device(self):
+        return self.buf.device
+
+
+def logmel_shape_error(n_fft, hop, n_mels):
+    """-> None if the general front-end takes the shape, else a message naming the violated limit."""
+    if not NFFT_MIN <= n_fft <= NFFT_MAX:
+        return "n_fft=%d outside %d..%d" % (n_fft, NFFT_MIN, NFFT_MAX)
+    if not 1 <= hop <= n_fft:
+        return "hop=%d outside 1..n_fft (%d)" % (hop, n_fft)
+    if not 1 <= n_mels <= NMELS_MAX:
+        return "n_mels=%d outside 1..%d" % (n_mels, NMELS_MAX)
+    return None
+
+
+def logmel_plan(window, fb, hop=160):
+    """Device plan for log-mel: window [n_fft], fb [n_fft//2 + 1, n_mels].  The default shape (400, hop 160, 80 mels) gets the
+    plan of tal_logmel_fwd (a uint8 tensor) unless the option `logmel_general` is set; any other shape a LogmelGeneralPlan."""
     lib = N.lib()
     window = _f32c(window, "logmel_plan(window)")
     fb = _f32c(fb, "logmel_plan(fb)")
-    if tuple(window.shape) != (400,) or tuple(fb.shape) != (201, 80):
-        raise N.NativeError("logmel_plan: window/fb must be [400] and [201, 80], got %s %s"
+    if window.dim() != 1 or fb.dim() != 2 or fb.shape[0] != window.shape[0] // 2 + 1:
+        raise N.NativeError("logmel_plan: window/fb must be [n_fft] and [n_fft//2 + 1, n_mels], got %s %s"
                             % (tuple(window.shape), tuple(fb.shape)))
+    n_fft, n_mels = int(window.shape[0]), int(fb.shape[1])
+    if (n_fft, hop, n_mels) != (400, 160, 80) or N.get_option("logmel_general"):
+        err = logmel_shape_error(n_fft, hop, n_mels)
+        if err:
+            raise N.NativeError("logmel_plan: " + err)
+        buf = torch.empty(lib.tal_logmel_general_plan_bytes(n_fft, n_mels), dtype=torch.uint8, device=window.device)
+        N.check(lib.tal_logmel_general_plan_init(N.ptr(window), n_fft, hop, N.ptr(fb), n_mels, N.ptr(buf), N.stream_handle()),
+                "tal_logmel_general_plan_init")
+        return LogmelGeneralPlan(buf, n_fft, hop, n_mels)
     plan = torch.empty(lib.tal_logmel_plan_bytes(), dtype=torch.uint8, device=window.device)
     N.check(lib.tal_logmel_plan_init(N.ptr(window), N.ptr(fb), N.ptr(plan), N.stream_handle()),
             "tal_logmel_plan_init")
@@ -47,12 +83,25 @@ def _audio(t, what):
 
 
 def logmel(plan, audio, eps=1e-6, subtract_mean=True, return_stats=False):
-    """audio [B, L] fp32 or fp16 -> [B, T, 80] fp32 (LogMelSpec.forward, tal/asr/models.py:35-53)."""
+    """audio [B, L] fp32 or fp16 -> [B, T, n_mels] fp32 (LogMelSpec.forward, tal/asr/models.py:35-53); T = 1 + L // hop as
+    torch.stft counts for even n_fft (the default plan: [B, T, 80]), 1 + (L - 1) // hop for odd n_fft."""
     lib = N.lib()
     audio = _audio(audio, "logmel")
     if audio.dim() != 2:
         raise N.NativeError("logmel: audio must be [batch, samples]")
     B, L = audio.shape
+    if isinstance(plan, LogmelGeneralPlan):
+        T = lib.tal_logmel_frames(L - plan.n_fft % 2, plan.hop)        # (torch.stft's count: one less for odd n_fft when hop | L)
+        out = torch.empty(B, T, plan.n_mels, dtype=torch.float32, device=audio.device)
+        mean = torch.empty(1, dtype=torch.float32, device=audio.device)
+        stats = torch.empty(2, dtype=torch.float64, device=audio.device)
+        nws = lib.tal_logmel_general_workspace_bytes(plan.n_fft, plan.hop, B, L)
+        ws = _ws(nws, audio.device)
+        N.check(lib.tal_logmel_general_fwd(N.ptr(plan.buf), plan.n_fft, plan.hop, plan.n_mels, N.ptr(audio),
+                                           1 if audio.dtype == torch.float16 else 0, B, L, eps, 1 if subtract_mean else 0,
+                                           N.ptr(out), N.ptr(mean), N.ptr(stats), N.ptr(ws), nws, N.stream_handle()),
+                "tal_logmel_general_fwd")
+        return (out, mean, stats) if return_stats else out
     T = lib.tal_logmel_num_frames(L)
     out = torch.empty(B, T, 80, dtype=torch.float32, device=audio.device)
     mean = torch.empty(1, dtype=torch.float32, device=audio.device)
