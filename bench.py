@@ -2,7 +2,7 @@
 """Headline benchmark: audio frames/s, waveform-on-device -> log-mel -> TDS encoder ->
 diarization head (128-d features + argmax speaker ids), BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W [--workload clip|segments|decode] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload clip|segments|decode] [--dump-outputs DIR] [--full]
 
 One process per GPU.  Typed as above with N > 1 and no WORLD_SIZE in the environment, the script starts its own N
 rank processes (127.0.0.1 rendezvous) before anything touches the GPU and prints rank 0's line; under
@@ -23,14 +23,20 @@ Workloads (a step = one pass of the hot path over synthetic input already reside
   decode    configs[4]: the joint decode of a 1-hour episode end to end -- ASR encode + sliding-window greedy decode
             (System.generate_unaligned) + SDModel pass + word-level WDER-format pooling / voting; one episode per GPU.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-  roofline     -- dominant kernel: algorithmic work / HIP-event time of its launches inside the timed region vs the
-                  peak it is bounded by
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's headline needs:
+set-up, the W warm-up steps, the timed passes of K steps (`value` is the median pass), --dump-outputs, the line.
+
+--full adds everything else the benchmark measures (each leg can still be left out with its --no-* option):
+  roofline     -- dominant kernel: algorithmic work / HIP-event time of its launches in a further pass of the K steps with
+                  per-launch events, vs the peak it is bounded by; `kernel_time_share`, `kernel_ms_per_step`
   cpu_baseline -- the CPU oracle (a port of the reference's PyTorch-CPU path) timed on this box's host cores (N = 1 only):
                   thread count chosen on a 5-minute sample, then the 1-hour clip itself at that count.
-The default N = 1 line also carries `per_rank_share` (what one rank of an 8 / 4 / 2 / 1-GPU run of configs[3] computes per
-step: 8 / 16 / 32 / 64 five-minute segments as one batched call) and `decode_episode` (configs[4] on a 5-minute episode with
-the CPU port of the same chain beside it).
+  the shader clock and socket power of every timed pass (`gpu_sclk_mhz`, `gpu_power_w`, `passes.clocks`); at N > 1 with the
+  segments workload, rank 0's solo pass over the same segments (`one_gpu_same_workload`, `speedup_vs_one_gpu`); with the
+  clip workload, `value_exact_f32` (the K steps on the exact fp32 kernels) and `h2d_ms_per_clip` / `value_including_h2d`,
+  and at N = 1 also `stream_of_clips_from_host`, `clip_latency` (30 s and 5 min clips), `per_rank_share` (what one rank of
+  an 8 / 4 / 2 / 1-GPU run of configs[3] computes per step: 8 / 16 / 32 / 64 five-minute segments as one batched call) and
+  `decode_episode` (configs[4] on a 5-minute episode with the CPU port of the same chain beside it).
 """
 import argparse
 import ctypes as C
@@ -79,7 +85,15 @@ def parse():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last step of the timed passes returned as DIR/<name>.npy (float32 / float64, <= 64 MB "
                          "in all: a fixed seeded sample of rows beyond that), for output-for-output comparison of two builds")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (module docstring): roofline, CPU baseline, clocks, the "
+                         "other precisions, clip lengths and batch sizes; the --no-* options leave single legs out")
     a = ap.parse_args()
+    if not a.full:
+        # a plain run: the headline alone, every leg beside the timed passes off
+        for leg in ("no_cpu_baseline", "no_prof", "no_exact_pass", "no_clip_latency", "no_per_rank_share", "no_decode_episode",
+                    "no_one_gpu_reference", "no_clock_sampler"):
+            setattr(a, leg, True)
     if a.workload is None:
         a.workload = "clip" if a.gpus == 1 else "segments"
     if a.seconds is None:
@@ -742,7 +756,7 @@ def main():
 
     # PCIe-inclusive figure (reported beside `value`, never as `value`): one pinned-host -> device copy
     h2d_ms = None
-    if rank == 0 and args.workload == "clip":
+    if args.full and rank == 0 and args.workload == "clip":
         host = clips[0].cpu().pin_memory()
         sync()
         t_h = time.perf_counter()
@@ -754,7 +768,7 @@ def main():
     # The same path fed from HOST memory as a stream of clips (the reference's loop over episodes, reconcile.py:96-102): the
     # upload of clip i + 1 runs on a copy stream under the compute of clip i (SDModel.speaker_ids_stream)
     streamed = None
-    if rank == 0 and args.workload == "clip" and not fake and world == 1:
+    if args.full and rank == 0 and args.workload == "clip" and not fake and world == 1:
         host = clips[0].cpu().pin_memory()
         n_stream = 6
         with torch.no_grad():

@@ -15,8 +15,8 @@ print({k: v for k, v in m.items() if "clk" in k or "power" in k or "temp" in k o
 PY
 (time timeout 2400 python -m pytest tests -m gpu -x -q --durations=25) > $O/pytest_gpu.txt 2>&1
 echo "pytest rc=$?" >> $O/pytest_gpu.txt
-python bench.py --steps 20 --warmup 3 > $O/bench_1h.json 2> $O/bench_1h.err
-python bench.py --steps 20 --warmup 3 --passes 7 --no-cpu-baseline --no-exact-pass --no-per-rank-share --no-clip-latency > $O/bench_1h_7passes.json 2> /dev/null
-python bench.py --steps 20 --warmup 3 --passes 7 --no-cpu-baseline --no-exact-pass --no-per-rank-share --no-clip-latency --no-decode-episode > $O/bench_1h_7passes_no_decode_episode.json 2> /dev/null
-python bench.py --steps 20 --warmup 3 --passes 7 --no-clock-sampler --no-cpu-baseline --no-exact-pass --no-per-rank-share --no-clip-latency --no-decode-episode > $O/bench_1h_7passes_no_sampler.json 2> /dev/null
+python bench.py --full --steps 20 --warmup 3 > $O/bench_1h.json 2> $O/bench_1h.err
+python bench.py --full --steps 20 --warmup 3 --passes 7 --no-cpu-baseline --no-exact-pass --no-per-rank-share --no-clip-latency > $O/bench_1h_7passes.json 2> /dev/null
+python bench.py --full --steps 20 --warmup 3 --passes 7 --no-cpu-baseline --no-exact-pass --no-per-rank-share --no-clip-latency --no-decode-episode > $O/bench_1h_7passes_no_decode_episode.json 2> /dev/null
+python bench.py --full --steps 20 --warmup 3 --passes 7 --no-clock-sampler --no-cpu-baseline --no-exact-pass --no-per-rank-share --no-clip-latency --no-decode-episode > $O/bench_1h_7passes_no_sampler.json 2> /dev/null
 tail -5 $O/pytest_gpu.txt

@@ -8,6 +8,6 @@ cd $R
 echo "pytest rc=$?" >> $O/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1
 echo "smoke rc=$?" >> $O/smoke.txt
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 grep -h "passed\|failed\|rc=" $O/pytest_gpu.txt $O/smoke.txt
 grep smoke $O/smoke.txt

@@ -17,6 +17,6 @@ TAL_OPTIONS=decode_no_fold python scripts/bench_greedy_step_multi.py 32 2>&1 | g
 python scripts/bench_episode.py 300 > $O/episode_5min_folded.txt 2>&1
 TAL_OPTIONS=decode_no_fold python scripts/bench_episode.py 300 > $O/episode_5min_unfolded.txt 2>&1
 python scripts/r6_uisrnn_predict.py > $O/uisrnn_predict.txt 2>&1
-python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-exact-pass --no-per-rank-share > $O/bench_1h.json 2> $O/bench_1h.err
+python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-exact-pass --no-per-rank-share > $O/bench_1h.json 2> $O/bench_1h.err
 tail -3 $O/pytest_decode.txt $O/pytest_determinism_decode.txt $O/pytest_parity_new.txt
 cat $O/decode_step_folded.txt $O/decode_step_unfolded.txt

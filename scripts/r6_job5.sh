@@ -9,6 +9,6 @@ echo "pytest rc=$?" >> $O/pytest_gpu.txt
 python scripts/bench_episode.py 300 > $O/episode_5min.txt 2>&1
 TAL_OPTIONS=decode_no_fold python scripts/bench_episode.py 300 > $O/episode_5min_unfolded.txt 2>&1
 python scripts/bench_episode.py 3600 > $O/episode_1h.txt 2>&1
-python bench.py --steps 20 --warmup 3 > $O/bench_1h.json 2> $O/bench_1h.err
+python bench.py --full --steps 20 --warmup 3 > $O/bench_1h.json 2> $O/bench_1h.err
 grep -h "passed\|failed\|rc=" $O/pytest_gpu.txt
 grep -h "rep 1" $O/episode_5min.txt $O/episode_5min_unfolded.txt $O/episode_1h.txt

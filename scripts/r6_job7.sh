@@ -9,6 +9,6 @@ echo "pytest rc=$?" >> $O/pytest_decode.txt
 echo "pytest rc=$?" >> $O/pytest_determinism_decode.txt
 python scripts/bench_episode.py 300 > $O/episode_5min.txt 2>&1
 python scripts/bench_episode.py 3600 > $O/episode_1h.txt 2>&1
-python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-exact-pass --no-per-rank-share --no-clip-latency > $O/bench_1h.json 2> /dev/null
+python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-exact-pass --no-per-rank-share --no-clip-latency > $O/bench_1h.json 2> /dev/null
 grep -h "passed\|failed\|rc=" $O/pytest_decode.txt $O/pytest_determinism_decode.txt
 grep -h "rep 1" $O/episode_5min.txt $O/episode_1h.txt

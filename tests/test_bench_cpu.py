@@ -1,5 +1,6 @@
 """bench.py on the CPU: --dump-outputs (the files, their dtypes, the 64 MB cap and the run-to-run identity of what is written),
-and loading the native library from a tree built beforehand that is read-only to the user who runs the benchmark.
+what a plain run leaves to --full, and loading the native library from a tree built beforehand that is read-only to the user
+who runs the benchmark.
 The end-to-end runs use the TAL_BENCH_FAKE plumbing mode (segments workload, deterministic tensors in place of GPU work)."""
 import json
 import os
@@ -67,6 +68,37 @@ def test_dump_outputs_cap_keeps_the_same_seeded_rows(tmp_path):
     t = np.load(tmp_path / "a" / "tokens.npy")
     assert t.dtype == np.float64 and 1 <= t.shape[0] <= 7 and t.shape[1] == 1
 
+
+LEGS = ("no_cpu_baseline", "no_prof", "no_exact_pass", "no_clip_latency", "no_per_rank_share", "no_decode_episode",
+        "no_one_gpu_reference", "no_clock_sampler")
+
+
+def test_plain_run_switches_every_other_leg_off(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and all(getattr(a, k) for k in LEGS)
+    assert (a.workload, a.steps, a.warmup, a.passes) == ("clip", 3, 1, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    a = bench.parse()
+    assert a.full and not any(getattr(a, k) for k in LEGS)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.no_cpu_baseline and not a.no_prof
+
+
+def test_full_adds_legs_and_keeps_the_timed_steps(tmp_path):
+    """--full adds what lies beside the headline (here: rank 0's solo pass over the same segments of a two-rank run); the
+    line's headline fields and the dumped outputs of the timed steps are those of the plain run."""
+    plain = _bench(tmp_path, "plain", "--gpus", "2", "--steps", "2", "--warmup", "1")
+    full = _bench(tmp_path, "full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--full")
+    assert "one_gpu_same_workload" not in plain and "speedup_vs_one_gpu" not in plain
+    assert full["one_gpu_same_workload"]["n_gpus"] == 1 and full["speedup_vs_one_gpu"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "n_gpus", "config"):
+        assert plain[k] == full[k], k
+    assert plain["ms_per_step"] > 0 and len(plain["ms_per_step_passes"]) == 3
+    for name in ("feat", "ids"):
+        np.testing.assert_array_equal(np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy")))
 
 
 def _refuse(*a, **k):

@@ -100,10 +100,10 @@ def _last_line(p):
 def test_bench_eight_rank_plan_of_configs3():
     """The exact plan of `bench.py --gpus 8 --workload segments` on an 8-GPU node -- 64 segments, 8 per rank by
     distributed.shard_indices, the gather plan's one all-reduce, one gather per step, the scalar mean all-reduce, rank 0's
-    same-workload reference pass -- as a CPU plumbing run (gloo, TAL_BENCH_FAKE), under the launcher the driver uses."""
+    same-workload reference pass (--full) -- as a CPU plumbing run (gloo, TAL_BENCH_FAKE), under the launcher the driver uses."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--seconds", "30"]
+           "--seconds", "30", "--full"]
     line = _last_line(subprocess.run(cmd, env=_bench_env(OMP_NUM_THREADS="1"), capture_output=True, text=True, timeout=600))
     assert line["n_gpus"] == 8 and line["scaling"] == "strong" and line["gathered_segments"] == 64
     assert line["config"]["frames_per_step"] == 64 * 3001 and "configs[3]" in line["config"]["workload"]

@@ -33,13 +33,14 @@ def test_bench_segments_two_ranks_on_the_real_kernels():
     """The exact code path the driver's multi-GPU run takes -- `bench.py --gpus 2 --workload segments` launched through
     torch.distributed.run -- on the real HIP kernels, with the gloo backend standing in for RCCL because the test box has
     one GPU (both ranks share it; results are staged through host memory): shard_indices, flat weight broadcast, the scalar
-    all-reduce of the log-mel mean, ONE packed gather per step, the same-workload one-GPU reference pass."""
+    all-reduce of the log-mel mean, ONE packed gather per step, and with --full the same-workload one-GPU reference pass and
+    the per-launch event pass the roofline comes from."""
     import json
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", TAL_BENCH_BACKEND="gloo")
     env.pop("TAL_BENCH_FAKE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "segments",
-           "--segments", "6", "--seconds", "20", "--steps", "2", "--warmup", "1"]
+           "--segments", "6", "--seconds", "20", "--steps", "2", "--warmup", "1", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
