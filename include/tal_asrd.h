@@ -44,7 +44,7 @@ extern "C" {
 #define TAL_MAX_STAGES 4
 #define TAL_MAX_DEPTH 8
 
-int tal_version(void);          /* 500 = 0.5.0 */
+int tal_version(void);          /* 501 = 0.5.1 */
 const char* tal_last_error(void);
 
 /* Process-wide behaviour switches.  The library never reads the environment: which kernels a caller gets depends on its
@@ -65,6 +65,8 @@ const char* tal_last_error(void);
  *   logmel_mfma           1: the log-mel front-end as the float64 matrix-core DFT instead of the fast transform (see tal_logmel_fwd)
  *   logmel_general        1: the host mirror builds general plans (tal_logmel_general_*) for the default 16 kHz / 80 shape too
  *                         (a comparison switch: the C calls themselves do not read it)
+ *   gconv_general         1: tal_tds_fwd runs every grouped conv on the any-k kernels (tal_gconv_*_k_fwd) at k = 21 too, with the
+ *                         dense layers in their usual forms (bit-identical under TAL_TDS_EXACT_F32; a comparison / A-B switch)
  *   gemm_s64_below        fp16x3 relu / residual layers run on 64 x 80 tiles without K slices while those tiles number
  *                         at most this many per CU (default 2; 0: never)
  *   gconv_short_below     grouped convs use 64-step tiles while the long tiles would give a CU fewer workgroups than
@@ -172,12 +174,15 @@ int tal_linear_f16x3_guarded_fwd(const void* x_split, const void* w_split, const
 
 /* ------------------------------------------------------------------ *
  * Grouped temporal convolutions of the TDS encoder.
- * Packed weight layout [G][C_in/G][21][C_out/G] (tal_pack_gconv_weight
- * converts from the reference's Conv1d layout [C_out, C_in/G, 21]).
+ * Packed weight layout [G][C_in/G][k][C_out/G] (tal_pack_gconv_weight
+ * converts from the reference's Conv1d layout [C_out, C_in/G, k];
+ * 1 <= k <= TAL_GCONV_MAX_K, the reference's default k = 21).
  * ------------------------------------------------------------------ */
+#define TAL_GCONV_MAX_K 63
 int tal_pack_gconv_weight(const float* w_ref, float* w_packed, int c_out, int c_in_per_group,
                           int ksize, int groups, void* stream);
-/* Conv1d(C_in->C_out, k=21, stride=2, groups=G, padding=0), models.py:363-364.
+/* The kernel-size-specialised forms below are built for k = 21; tal_gconv_s2_k_fwd / tal_gconv_res_k_fwd take any k.
+ * Conv1d(C_in->C_out, k=21, stride=2, groups=G, padding=0), models.py:363-364.
  * x [B, T_in, C_in] -> y [B, T_out, C_out], T_out = (T_in-21)/2 + 1. */
 int tal_gconv_s2_fwd(const float* x, const float* w_packed, const float* bias, int B, int64_t T_in,
                      int C_in, int C_out, int groups, float* y, void* stream);
@@ -185,6 +190,17 @@ int tal_gconv_s2_fwd(const float* x, const float* w_packed, const float* bias, i
  * Zero padding at the true ends of each batch item. */
 int tal_gconv_res_fwd(const float* x, const float* w_packed, const float* bias, float alpha, int B,
                       int64_t T, int C, int groups, float* y, void* stream);
+/* The same two convs at any kernel size (csrc/gconv_general.hip): exact fp32, each output starts from its bias and takes one fmaf
+ * per product, input channel outer and tap inner -- the order of the k = 21 kernels above, so at k = 21 the results are theirs bit
+ * for bit.  w_packed from tal_pack_gconv_weight with the same ksize.
+ * tal_gconv_s2_k_fwd:  stride 2, padding 0, 1 <= ksize <= TAL_GCONV_MAX_K (even allowed), T_in >= ksize:
+ *                      [B, T_in, C_in] -> [B, (T_in - ksize) / 2 + 1, C_out].
+ * tal_gconv_res_k_fwd: y = x + alpha * relu(Conv1d(C->C, ksize, groups=G, padding=ksize/2)(x)), odd ksize; zero padding at
+ *                      the true ends of each batch item. */
+int tal_gconv_s2_k_fwd(const float* x, const float* w_packed, const float* bias, int B, int64_t T_in, int C_in, int C_out,
+                       int groups, int ksize, float* y, void* stream);
+int tal_gconv_res_k_fwd(const float* x, const float* w_packed, const float* bias, float alpha, int B, int64_t T, int C,
+                        int groups, int ksize, float* y, void* stream);
 
 /* The grouped convs on the fp16 matrix cores in the fp16x3 form of the dense layers (three fp16 MFMAs per fp32 product
  * block, fp32 accumulation; error against float64 below an fp32 fmaf chain).  Built for the TDSBlock conv (stride 1,
@@ -238,14 +254,16 @@ typedef struct tal_tds_desc {
     tal_tds_block_w blocks[TAL_MAX_STAGES][TAL_MAX_DEPTH];
     const void* down_w_frag[TAL_MAX_STAGES]; /* stride-2 conv weights as fp16x3 MFMA fragments, or NULL (VALU kernel) */
     int32_t flags;                    /* TAL_TDS_EXACT_F32: every layer on the exact fp32-input kernels (no fp16x3 form) */
-    int32_t _pad2;
+    int32_t ksize;                    /* kernel size of every grouped conv (TDS(..., kernel_size)): 0 or 21 = the reference default;
+                                       * else 1..TAL_GCONV_MAX_K, odd wherever depths[i] > 0.  k != 21 runs every grouped conv on the
+                                       * exact fp32 any-k kernels (tal_gconv_*_k_fwd) and needs NULL down_w_frag / conv_w_frag */
 } tal_tds_desc;
 #define TAL_TDS_EXACT_F32 1
 #define TAL_TDS_OUT_SPLIT 2   /* leave y in the hi / lo split form where the last stage runs all-split (tal_tds_out_split() says whether
                                * a call will): for tal_sd_head_split_fwd, whose embedding layer consumes that form -- the last dense layer
                                * then never writes an fp32 copy of the encoder output */
 
-/* output length after all stride-2 stages: T' = f(f(f(T))), f(t) = (t-21)/2+1 */
+/* output length after all stride-2 stages: T' = f(f(f(T))), f(t) = (t-k)/2+1 (0 below k), k = the descriptor's ksize */
 int64_t tal_tds_out_len(const tal_tds_desc* d, int64_t T);
 size_t tal_tds_workspace_bytes(const tal_tds_desc* d, int B, int64_t T);
 /* fp16-range guard.  The fp16x3 form carries fp32 values as two fp16 halves, so it needs |x| <= 65504 for every
@@ -262,7 +280,8 @@ size_t tal_tds_status_offset(const tal_tds_desc* d, int B, int64_t T);
  * A PREDICTION (made for a 16-byte aligned x under the options in force at the time of the query): the call itself records the
  * form it wrote in word 1 of its status block (int32 at tal_tds_status_offset() + 4: 1 = split, 0 = fp32), and a caller that
  * hands y to tal_sd_head_split_fwd on the strength of the prediction reads that word together with the range flag.
- * tal_tds_tiled_fwd always writes fp32 (the flag is ignored there). */
+ * tal_tds_tiled_fwd always writes fp32 (the flag is ignored there).  Always 0 for a descriptor with ksize != 21 (or under the
+ * option gconv_general): its grouped convs have no split form. */
 int tal_tds_out_split(const tal_tds_desc* d, int B, int64_t T);
 /* x [B, T, channels[0]] -> y [B, T', channels[n_stages]] */
 int tal_tds_fwd(const tal_tds_desc* d, const float* x, int B, int64_t T, float* y,
@@ -272,7 +291,8 @@ int tal_tds_fwd(const tal_tds_desc* d, const float* x, int B, int64_t T, float* 
  * resize conv has no padding (models.py:363-364), so conv(x - m) = conv(x) - m * sum_k w[k]: the subtraction is applied as a
  * correction of that conv's bias and the separate pass over the log-mel (two activation-sized transfers and a launch) is not run.
  * Same workspace, status word and re-run rule as tal_tds_fwd.  Only for stacks whose first resize conv is the 1 -> 10 channels
- * per group form (tal_tds_premean_ok() != 0: the reference's 80 -> 800 encoder, x 16-byte aligned); TAL_EINVAL otherwise.
+ * per group form (tal_tds_premean_ok() != 0: the reference's 80 -> 800 encoder at k = 21, x 16-byte aligned, option gconv_general
+ * off); TAL_EINVAL otherwise.
  * Results differ from tal_tds_fwd on the subtracted tensor by fp32 rounding of the first conv only. */
 int tal_tds_premean_ok(const tal_tds_desc* d, const float* x);
 int tal_tds_premean_fwd(const tal_tds_desc* d, const float* x, const float* x_mean, int B, int64_t T, float* y,
@@ -281,7 +301,7 @@ int tal_tds_premean_fwd(const tal_tds_desc* d, const float* x, const float* x_me
 /* Time-tiled form of the same call for ONE item (SURVEY.md section 8b `halo_mode`): the input is cut into tiles of
  * `out_tile` output frames; each tile runs as its own tal_tds_fwd over the slice of x that carries its receptive-field halo
  * (tal_tds_halo: output frame t reads the input frames [stride t - left, stride t + right]; 640 / 780 / 8 for the 2 / 3 / 6
- * block stack) and reproduces its frames as the whole sequence would -- slices start at multiples of the stride, and at a
+ * block stack at k = 21, 448 / 546 / 8 at k = 15) and reproduces its frames as the whole sequence would -- slices start at multiples of the stride, and at a
  * true end of the sequence the blocks' zero padding is the same in the slice.  For items beyond the 2 GiB-per-item limit
  * of the fp16x3 kernels' 32-bit offsets (~3.7 h of audio), which would otherwise take the generic kernels, and for
  * bounding the workspace.  The fp16-range status word of the whole call (OR over the tiles) sits at

@@ -14,6 +14,7 @@ TAL_MAX_STAGES = 4
 TAL_MAX_DEPTH = 8
 TAL_TDS_EXACT_F32 = 1
 TAL_TDS_OUT_SPLIT = 2
+TAL_GCONV_MAX_K = 63    # largest kernel size of the grouped convs (any-k kernels, csrc/gconv_general.hip)
 TAL_GROUP_MAX = 16      # sessions per merged decode step (csrc/common.h)
 
 c_float_p = C.c_void_p  # device pointers travel as integers
@@ -30,7 +31,7 @@ class TdsDesc(C.Structure):
                 ("channels", C.c_int32 * (TAL_MAX_STAGES + 1)), ("depths", C.c_int32 * TAL_MAX_STAGES),
                 ("down_w", C.c_void_p * TAL_MAX_STAGES), ("down_b", C.c_void_p * TAL_MAX_STAGES),
                 ("blocks", (TdsBlockW * TAL_MAX_DEPTH) * TAL_MAX_STAGES),
-                ("down_w_frag", C.c_void_p * TAL_MAX_STAGES), ("flags", C.c_int32), ("_pad2", C.c_int32)]
+                ("down_w_frag", C.c_void_p * TAL_MAX_STAGES), ("flags", C.c_int32), ("ksize", C.c_int32)]
 
 
 class DecoderLayerW(C.Structure):
@@ -94,6 +95,8 @@ SIGNATURES = {
     "tal_pack_gconv_weight": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "tal_gconv_s2_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _p, _p]),
     "tal_gconv_res_fwd": (_i, [_p, _p, _p, _f, _i, _i64, _i, _i, _p, _p]),
+    "tal_gconv_s2_k_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _i, _p, _p]),
+    "tal_gconv_res_k_fwd": (_i, [_p, _p, _p, _f, _i, _i64, _i, _i, _i, _p, _p]),
     "tal_gconv_f16x3_weight_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "tal_pack_gconv_f16x3_weight": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "tal_gconv_s2_f16x3_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _p, _p]),

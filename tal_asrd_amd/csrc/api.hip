@@ -20,8 +20,8 @@ void set_error(const char* fmt, ...) {
 // ---- behaviour switches (tal_set_option) ---------------------------------------------------
 static const char* const g_opt_names[OPT_COUNT] = {
     "tds_exact_f32", "tds_fp32_activations", "gconv_fuse_split", "gconv_c1_generic", "head_no_astationary", "gemm_global_loads",
-    "gemm_no_splitk4", "gemm_no_glds", "gemm_no_splitk_tail", "gemm_no_w64", "logmel_no_fold", "decode_no_small", "decode_small_rows", "gemm_no_row_split", "gemm_no_n96", "gemm_s64_below", "gconv_short_below", "gconv_no_shift18", "gconv_grid_xyz", "gemm_w64_stagger", "gemm_s64_order", "decode_wide_gemm", "gemm_s64_rows", "decode_persist", "decode_persist_wgs", "logmel_mfma", "gru_unfused", "decode_no_fold", "gconv_c1_fuse", "decode_fold_rows", "gconv_long_tt", "logmel_general"};
-static std::atomic<int> g_opt[OPT_COUNT] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {256}, {0}, {0}, {2}, {4}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {32}, {0}, {0}, {0}, {0}, {64}, {0}, {0}};
+    "gemm_no_splitk4", "gemm_no_glds", "gemm_no_splitk_tail", "gemm_no_w64", "logmel_no_fold", "decode_no_small", "decode_small_rows", "gemm_no_row_split", "gemm_no_n96", "gemm_s64_below", "gconv_short_below", "gconv_no_shift18", "gconv_grid_xyz", "gemm_w64_stagger", "gemm_s64_order", "decode_wide_gemm", "gemm_s64_rows", "decode_persist", "decode_persist_wgs", "logmel_mfma", "gru_unfused", "decode_no_fold", "gconv_c1_fuse", "decode_fold_rows", "gconv_long_tt", "logmel_general", "gconv_general"};
+static std::atomic<int> g_opt[OPT_COUNT] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {256}, {0}, {0}, {2}, {4}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {32}, {0}, {0}, {0}, {0}, {64}, {0}, {0}, {0}};
 int opt(Option o) { return g_opt[o].load(std::memory_order_relaxed); }
 
 int device_cus() {
@@ -181,13 +181,14 @@ int launch_argmax_rows(const float* x, int64_t M, int N, int32_t* ids, hipStream
     return TAL_OK;
 }
 
-static int64_t conv_out_len(int64_t t) { return t < 21 ? 0 : (t - 21) / 2 + 1; }
+// stride-2, padding-0 resize conv of kernel size k (tal/asr/models.py:363-364)
+static int64_t conv_out_len(int64_t t, int k) { return t < k ? 0 : (t - k) / 2 + 1; }
 
 }  // namespace tal
 
 using namespace tal;
 
-extern "C" int tal_version(void) { return 500; /* 0.5.0: tal_greedy_ctx grew (needs_reset, pick_bias, no_fold), tal_decoder_layer_w grew (fold_*), tal_greedy_step_poll takes a non-const context, word 1 of the TDS status block = output form, options gru_unfused / decode_no_fold / decode_fold_rows / gconv_c1_fuse; 0.4.3: log-mel as a fast transform (option logmel_mfma: the matrix form), the plan grew; 0.4.2: TAL_TDS_OUT_SPLIT, tal_tds_out_split, tal_sd_head_split_fwd; 0.4.1: tal_tds_premean_fwd / tal_tds_premean_ok; 0.4.0: tal_greedy_ctx grew (k_pitch, episode-wide K | V table), merged decode steps, tal_unaligned_*, tal_logmel_f16_fwd; 0.3.0: tal_set_option */ }
+extern "C" int tal_version(void) { return 501; /* 0.5.1: TDS kernel size as a runtime value (tal_tds_desc._pad2 became ksize, TAL_GCONV_MAX_K, tal_gconv_s2_k_fwd / tal_gconv_res_k_fwd, tal_pack_gconv_weight takes 1..63, option gconv_general); 0.5.0: tal_greedy_ctx grew (needs_reset, pick_bias, no_fold), tal_decoder_layer_w grew (fold_*), tal_greedy_step_poll takes a non-const context, word 1 of the TDS status block = output form, options gru_unfused / decode_no_fold / decode_fold_rows / gconv_c1_fuse; 0.4.3: log-mel as a fast transform (option logmel_mfma: the matrix form), the plan grew; 0.4.2: TAL_TDS_OUT_SPLIT, tal_tds_out_split, tal_sd_head_split_fwd; 0.4.1: tal_tds_premean_fwd / tal_tds_premean_ok; 0.4.0: tal_greedy_ctx grew (k_pitch, episode-wide K | V table), merged decode steps, tal_unaligned_*, tal_logmel_f16_fwd; 0.3.0: tal_set_option */ }
 
 // Host-side helper of the decode loop (no device work): ngram_repeat_mask(row, n).sum() of tal/asr/util.py:5-17 -- the number
 // of positions covered by an n-gram that already occurred earlier in the row; like the reference, n-gram starts run to
@@ -341,29 +342,46 @@ extern "C" int tal_argmax_rows(const float* x, int64_t M, int N, int32_t* ids, v
 // ---------------------------------------------------------------------------------------
 // TDS encoder driver
 // ---------------------------------------------------------------------------------------
+// kernel size of the descriptor's grouped convs (0: the reference default 21)
+static int tds_ksize(const tal_tds_desc* d) { return d->ksize == 0 ? 21 : d->ksize; }
+// every grouped conv on the any-k kernels (csrc/gconv_general.hip): k != 21, or the comparison option at k = 21
+static bool tds_general(const tal_tds_desc* d) { return tds_ksize(d) != 21 || opt(OPT_GCONV_GENERAL) != 0; }
+
 static int check_desc(const tal_tds_desc* d) {
     TAL_CHECK_ARG(d, "tal_tds: null descriptor");
     TAL_CHECK_ARG(d->n_stages >= 1 && d->n_stages <= TAL_MAX_STAGES, "tal_tds: n_stages=%d", d->n_stages);
     TAL_CHECK_ARG(d->groups > 0, "tal_tds: groups=%d", d->groups);
+    TAL_CHECK_ARG(d->ksize >= 0 && d->ksize <= TAL_GCONV_MAX_K, "tal_tds: ksize=%d outside 1..%d (0: 21)", d->ksize, TAL_GCONV_MAX_K);
     for (int i = 0; i <= d->n_stages; ++i)
         TAL_CHECK_ARG(d->channels[i] > 0 && d->channels[i] % d->groups == 0, "tal_tds: channels[%d]=%d", i, d->channels[i]);
     for (int i = 0; i < d->n_stages; ++i) {
         TAL_CHECK_ARG(d->depths[i] >= 0 && d->depths[i] <= TAL_MAX_DEPTH, "tal_tds: depths[%d]=%d", i, d->depths[i]);
         TAL_CHECK_ARG(d->channels[i + 1] % 4 == 0 || d->depths[i] == 0, "tal_tds: channels[%d]=%d must be a multiple of 4 for the pointwise layers", i + 1, d->channels[i + 1]);
+        // the reference's TDSBlock adds conv(x) to x: an even k returns T + 1 frames and the add fails
+        TAL_CHECK_ARG(tds_ksize(d) % 2 == 1 || d->depths[i] == 0, "tal_tds: ksize=%d is even but depths[%d]=%d: a TDSBlock needs an odd kernel size",
+                      d->ksize, i, d->depths[i]);
+        if (tds_ksize(d) != 21) {
+            // the matrix-core fragments are packed for k = 21 only
+            TAL_CHECK_ARG(!d->down_w_frag[i], "tal_tds: down_w_frag[%d] set with ksize=%d (fragments exist for k = 21 only)", i, d->ksize);
+            for (int j = 0; j < d->depths[i]; ++j)
+                TAL_CHECK_ARG(!d->blocks[i][j].conv_w_frag, "tal_tds: blocks[%d][%d].conv_w_frag set with ksize=%d (fragments exist for k = 21 only)",
+                              i, j, d->ksize);
+        }
     }
     return TAL_OK;
 }
 
 extern "C" int64_t tal_tds_out_len(const tal_tds_desc* d, int64_t T) {
     if (!d) return -1;
-    for (int i = 0; i < d->n_stages; ++i) T = conv_out_len(T);
+    const int k = tds_ksize(d);
+    for (int i = 0; i < d->n_stages; ++i) T = conv_out_len(T, k);
     return T;
 }
 
 static size_t tds_buf_floats(const tal_tds_desc* d, int B, int64_t T) {
     size_t mx = 0;
     for (int i = 0; i < d->n_stages; ++i) {
-        T = conv_out_len(T);
+        T = conv_out_len(T, tds_ksize(d));
         const size_t n = (size_t)B * (size_t)T * (size_t)d->channels[i + 1];
         if (n > mx) mx = n;
     }
@@ -406,7 +424,7 @@ extern "C" int tal_tds_fwd(const tal_tds_desc* d, const float* x, int B, int64_t
 }
 
 extern "C" int tal_tds_premean_ok(const tal_tds_desc* d, const float* x) {
-    if (check_desc(d) || d->n_stages < 1) return 0;
+    if (check_desc(d) || d->n_stages < 1 || tds_general(d)) return 0;   // (the any-k kernels have no mean-folding form)
     return gconv_s2_can_fold_mean(d->channels[0], d->channels[1], d->groups, x) ? 1 : 0;
 }
 
@@ -422,15 +440,15 @@ extern "C" int tal_tds_premean_fwd(const tal_tds_desc* d, const float* x, const 
 
 // Which form a stage of the stack runs in is decided from the descriptor and the shapes alone (tal_tds_fwd and tal_tds_out_split share it).
 static bool tds_s2_mfma_ok(const tal_tds_desc* d, int B, int i, int64_t Tin, bool force_f32) {       // stride-2 resize conv of stage i on the matrix cores
-    return !force_f32 && d->down_w_frag[i] && (int64_t)B * conv_out_len(Tin) > 64 &&
+    return !force_f32 && !tds_general(d) && d->down_w_frag[i] && (int64_t)B * conv_out_len(Tin, 21) > 64 &&
            gconv_f16x3_weight_bytes(d->channels[i], d->channels[i + 1], d->groups, 2) > 0 && gconv_f16x3_fits(Tin, d->channels[i]);
 }
 static bool tds_stage_allsplit(const tal_tds_desc* d, int B, int64_t T, int i, const float* xin, bool in_split, bool force_f32, bool no_allsplit) {
-    if (force_f32 || no_allsplit || i >= d->n_stages || d->depths[i] == 0) return false;
+    if (force_f32 || no_allsplit || i >= d->n_stages || d->depths[i] == 0 || tds_general(d)) return false;
     const int c = d->channels[i + 1], cin = d->channels[i];
     int64_t Tin = T;
-    for (int q = 0; q < i; ++q) Tin = conv_out_len(Tin);
-    const int64_t To = conv_out_len(Tin), M = (int64_t)B * To;
+    for (int q = 0; q < i; ++q) Tin = conv_out_len(Tin, 21);
+    const int64_t To = conv_out_len(Tin, 21), M = (int64_t)B * To;
     if (M <= 128 || c % 160 != 0 || c % 32 != 0 || !gconv_f16x3_fits(To, c) || gconv_f16x3_weight_bytes(c, c, d->groups, 1) == 0) return false;
     for (int j = 0; j < d->depths[i]; ++j)
         if (!d->blocks[i][j].fc0_w_split || !d->blocks[i][j].fc3_w_split || !d->blocks[i][j].conv_w_frag) return false;
@@ -447,7 +465,7 @@ static bool tds_last_stage_allsplit(const tal_tds_desc* d, int B, int64_t T, con
     int64_t Tc = T;
     bool allsplit = false;
     for (int i = 0; i < d->n_stages; ++i) {
-        const int64_t To = conv_out_len(Tc);
+        const int64_t To = conv_out_len(Tc, tds_ksize(d));
         // (stage 0 reads the caller's fp32 x: its alignment matters to the 1 -> 10 kernel; later stages read workspace buffers)
         allsplit = tds_stage_allsplit(d, B, T, i, i == 0 ? x0 : reinterpret_cast<const float*>(static_cast<uintptr_t>(16)), cur_split, force_f32, no_allsplit);
         const bool last_stage = i == d->n_stages - 1;
@@ -464,7 +482,7 @@ static int tds_fwd_impl(const tal_tds_desc* d, const float* x, const float* x_me
     int rc = check_desc(d);
     if (rc) return rc;
     TAL_CHECK_ARG(x && y && workspace, "tal_tds_fwd: null pointer");
-    TAL_CHECK_ARG(B > 0 && tal_tds_out_len(d, T) > 0, "tal_tds_fwd: T=%lld too short for %d stride-2 k=21 stages", (long long)T, d->n_stages);
+    TAL_CHECK_ARG(B > 0 && tal_tds_out_len(d, T) > 0, "tal_tds_fwd: T=%lld too short for %d stride-2 k=%d stages", (long long)T, d->n_stages, tds_ksize(d));
     if (workspace_bytes < tal_tds_workspace_bytes(d, B, T)) {
         set_error("tal_tds_fwd: workspace %zu < %zu bytes", workspace_bytes, tal_tds_workspace_bytes(d, B, T));
         return TAL_ENOMEM;
@@ -495,16 +513,18 @@ static int tds_fwd_impl(const tal_tds_desc* d, const float* x, const float* x_me
     // separate split pass exist inside such a stage: 7 activation-sized transfers per block instead of 10.  Short inputs,
     // odd widths and the exact mode keep fp32 activations (the kernels below the `else`).
     const bool no_allsplit = opt(OPT_TDS_FP32_ACTIVATIONS) != 0;
-    auto stage_len = [&](int i) { int64_t t = T; for (int q = 0; q <= i; ++q) t = conv_out_len(t); return t; };
     auto s2_mfma_ok = [&](int i, int64_t Tin) { return tds_s2_mfma_ok(d, B, i, Tin, force_f32); };
     auto stage_allsplit = [&](int i, const float* xin, bool in_split) { return tds_stage_allsplit(d, B, T, i, xin, in_split, force_f32, no_allsplit); };
     const float* cur = x;
     bool cur_split = false;
     int ia = -1;
     int64_t Tc = T;
+    const int ks = tds_ksize(d);
+    // k != 21 (or the option gconv_general): every grouped conv on the exact fp32 any-k kernels; the dense layers keep their forms
+    const bool general = tds_general(d);
     for (int i = 0; i < d->n_stages; ++i) {
         const int cin = d->channels[i], c = d->channels[i + 1];
-        const int64_t To = conv_out_len(Tc);
+        const int64_t To = conv_out_len(Tc, ks);
         const bool last_stage = i == d->n_stages - 1;
         const int64_t M = (int64_t)B * To;
         const bool allsplit = stage_allsplit(i, cur, cur_split);
@@ -515,7 +535,7 @@ static int tds_fwd_impl(const tal_tds_desc* d, const float* x, const float* x_me
         // first TDSBlock conv's launch -- its output is computed straight into that kernel's LDS slab and never touches memory.  Bit-identical
         // and one launch + 1.15 GB of traffic per hour of audio less, but the conv's 3 G multiply-adds cost the same ~0.25 ms inside the
         // matrix-core kernel as in a launch of their own (profiles/r6_gconv_c1_fusion.txt): measured, kept for the record, not the default
-        const bool c1_fused = allsplit && i == 0 && !cur_split && !s2_mfma_ok(i, Tc) && d->depths[i] > 0 && opt(OPT_GCONV_C1_FUSE) &&
+        const bool c1_fused = !general && allsplit && i == 0 && !cur_split && !s2_mfma_ok(i, Tc) && d->depths[i] > 0 && opt(OPT_GCONV_C1_FUSE) &&
                               !opt(OPT_GCONV_C1_GENERIC) && gconv_c1_res_fusable(cin, c, d->groups, cur);
         if (c1_fused) {
             rc = TAL_OK;
@@ -528,7 +548,9 @@ static int tds_fwd_impl(const tal_tds_desc* d, const float* x, const float* x_me
             TAL_CHECK_ARG(!cur_split, "tal_tds_fwd: internal: stage %d would read a split activation through an fp32 kernel", i);
             // stride-2 resize conv: on the matrix cores when the fragments are there (10 -> 14, 14 -> 18 per group); it pays from
             // ~a hundred output steps on: 358 steps of 18 channels per group take 13 us against 57
-            if (s2_mfma_ok(i, Tc))
+            if (general)
+                rc = launch_gconv_s2_k(cur, d->down_w[i], d->down_b[i], B, Tc, cin, c, d->groups, ks, a, s);
+            else if (s2_mfma_ok(i, Tc))
                 rc = launch_gconv_s2_f16x3(cur, d->down_w_frag[i], d->down_b[i], B, Tc, cin, c, d->groups, a, s, range_flag);
             else
                 rc = launch_gconv_s2(cur, d->down_w[i], d->down_b[i], B, Tc, cin, c, d->groups, a, s, nullptr, nullptr, i == 0 ? x_mean : nullptr);
@@ -565,10 +587,12 @@ static int tds_fwd_impl(const tal_tds_desc* d, const float* x, const float* x_me
                 continue;
             }
             const bool f16x3 = !force_f32 && bw.fc0_w_split && bw.fc3_w_split && M > 128 && c % 160 == 0;
-            const bool conv_mfma = !force_f32 && M > 64 && bw.conv_w_frag && gconv_f16x3_weight_bytes(c, c, d->groups, 1) > 0 && gconv_f16x3_fits(To, c);
+            const bool conv_mfma = !force_f32 && !general && M > 64 && bw.conv_w_frag && gconv_f16x3_weight_bytes(c, c, d->groups, 1) > 0 && gconv_f16x3_fits(To, c);
             // x1 = x + rw * relu(gconv(x))            : a -> x1
             const bool fuse_split = opt(OPT_GCONV_FUSE_SPLIT) != 0;
-            if (conv_mfma)
+            if (general)
+                rc = launch_gconv_res_k(a, bw.conv_w, bw.conv_b, bw.resweight, B, To, c, d->groups, ks, x1, s);
+            else if (conv_mfma)
                 rc = launch_gconv_res_f16x3(a, bw.conv_w_frag, bw.conv_b, bw.resweight, B, To, c, d->groups, x1, (fuse_split && f16x3) ? x1s : nullptr, s,
                                             range_flag);
             else
@@ -610,16 +634,17 @@ static int tds_fwd_impl(const tal_tds_desc* d, const float* x, const float* x_me
 // Time-tiled encoder (SURVEY section 8b `halo_mode`): one long item as tiles with the receptive-field halo
 // ---------------------------------------------------------------------------------------
 // Output frame t of the stack reads the input frames [stride t - left, stride t + right]: per stage (from the last one
-// down) `depth` TDSBlocks of +-10 frames at that resolution, below them the stride-2 k = 21 conv (frame u reads [2 u, 2 u + 20]).
+// down) `depth` TDSBlocks of +-k/2 frames at that resolution, below them the stride-2 conv (frame u reads [2 u, 2 u + k - 1]).
 extern "C" int tal_tds_halo(const tal_tds_desc* d, int64_t* left, int64_t* right, int64_t* stride) {
     int rc = check_desc(d);
     if (rc) return rc;
+    const int k = tds_ksize(d);
     int64_t lo = 0, hi = 0, st = 1;
     for (int i = d->n_stages - 1; i >= 0; --i) {
-        lo -= (int64_t)d->depths[i] * 10;
-        hi += (int64_t)d->depths[i] * 10;
+        lo -= (int64_t)d->depths[i] * (k / 2);
+        hi += (int64_t)d->depths[i] * (k / 2);
         lo = 2 * lo;
-        hi = 2 * hi + 20;
+        hi = 2 * hi + k - 1;
         st *= 2;
     }
     if (left) *left = -lo;

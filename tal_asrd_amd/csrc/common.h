@@ -128,6 +128,7 @@ enum Option {
     OPT_DECODE_FOLD_ROWS,         // the folded decoder layer is taken up to this many rows (prefix tokens) per problem (default 64)
     OPT_GCONV_LONG_TT,            // long inputs, 10- / 14-channel TDSBlock convs: 0 = 256- / 128-step tiles (default), 256 / 128 = that length for both
     OPT_LOGMEL_GENERAL,           // the host mirror builds general log-mel plans (csrc/logmel_general.hip) for the default 16 kHz / 80 shape too
+    OPT_GCONV_GENERAL,            // tal_tds_fwd runs every grouped conv on the any-k kernels (csrc/gconv_general.hip) at k = 21 too
     OPT_COUNT
 };
 int opt(Option o);
@@ -225,6 +226,12 @@ bool gconv_s2_can_split(int C_in, int C_out, int groups, const float* x);
 bool gconv_s2_can_fold_mean(int C_in, int C_out, int groups, const float* x);
 int launch_gconv_res(const float* x, const float* wp, const float* bias, float alpha, int B, int64_t T, int C,
                      int groups, float* y, hipStream_t s);
+// the same convs at any kernel size 1..TAL_GCONV_MAX_K (csrc/gconv_general.hip; the block conv: odd k): exact fp32, the fmaf order of
+// the two above, so bit-identical to them at k = 21
+int launch_gconv_s2_k(const float* x, const float* wp, const float* bias, int B, int64_t T_in, int C_in, int C_out, int groups,
+                      int ks, float* y, hipStream_t s);
+int launch_gconv_res_k(const float* x, const float* wp, const float* bias, float alpha, int B, int64_t T, int C, int groups, int ks,
+                       float* y, hipStream_t s);
 size_t gconv_f16x3_weight_bytes(int C_in, int C_out, int groups, int stride);
 bool gconv_f16x3_fits(int64_t T, int C);
 // first resize conv (1 -> 10 channels per group) + first TDSBlock conv of the stage in one launch (gconv_mfma_kernel<.., FROMC1>)

@@ -1,4 +1,5 @@
-// Grouped temporal convolutions of the TDS encoder (k = 21, groups = n_mels = 80).
+// Grouped temporal convolutions of the TDS encoder at the reference's default kernel size k = 21 (groups = n_mels = 80;
+// any other k: csrc/gconv_general.hip).
 //
 //   stride-2 "resize" conv, padding 0 ........ tal/asr/models.py:363-364
 //   TDSBlock grouped conv + ReLU + ReZero ..... tal/asr/models.py:304-308,329
@@ -1663,7 +1664,7 @@ extern "C" int tal_debug_gconv_timeline(void* host_out) {
 extern "C" int tal_pack_gconv_weight(const float* w_ref, float* w_packed, int c_out, int c_in_per_group, int ksize,
                                      int groups, void* stream) {
     TAL_CHECK_ARG(w_ref && w_packed, "tal_pack_gconv_weight: null pointer");
-    TAL_CHECK_ARG(ksize == tal::KS, "tal_pack_gconv_weight: kernel size %d (only 21 is built)", ksize);
+    TAL_CHECK_ARG(ksize >= 1 && ksize <= TAL_GCONV_MAX_K, "tal_pack_gconv_weight: kernel size %d outside 1..%d", ksize, TAL_GCONV_MAX_K);
     TAL_CHECK_ARG(groups > 0 && c_out % groups == 0 && c_in_per_group > 0, "tal_pack_gconv_weight: bad shape");
     const int total = c_out * c_in_per_group * ksize;
     hipLaunchKernelGGL(tal::pack_gconv_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_ref,

@@ -224,7 +224,7 @@ def encode_clip_sharded(encoder, mel: torch.Tensor, out_tile: int, dst: int = 0,
     stitched encoder output [1, T', C'] (None elsewhere).  No collective but the final gather."""
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
-    plan = tiling.plan_tiles(int(mel.shape[1]), out_tile, tuple(encoder.depths))
+    plan = tiling.plan_tiles(int(mel.shape[1]), out_tile, tuple(encoder.depths), getattr(encoder, "kernel_size", tiling.KERNEL_SIZE))
     if not plan:
         return torch.zeros(1, 0, encoder.sizes[-1], dtype=torch.float32, device=mel.device) if rank == dst else None
     mine = tiling.shard_tiles(plan, rank, world)

@@ -32,7 +32,16 @@ from . import tiling
 from .modules import PositionalEncoding, weight_init
 
 DEFAULT_SR = 16000  # tal/asr/data/__init__.py:6
-KERNEL_SIZE = 21
+KERNEL_SIZE = 21    # the reference's default TDS kernel size (tal/asr/models.py:354); any 1..TAL_GCONV_MAX_K is built
+
+
+def _check_kernel_size(who, kernel_size, blocks):
+    """TDS / TDSBlock kernel sizes the HIP kernels take: 1..TAL_GCONV_MAX_K, odd where a TDSBlock uses it."""
+    if isinstance(kernel_size, bool) or not isinstance(kernel_size, int) or not 1 <= kernel_size <= N.TAL_GCONV_MAX_K:
+        raise N.NativeError("%s: kernel_size=%r outside 1..%d (the grouped-conv kernels' range)" % (who, kernel_size, N.TAL_GCONV_MAX_K))
+    if blocks and kernel_size % 2 == 0:
+        raise N.NativeError("%s: kernel_size=%d is even: the reference's TDSBlock residual add fails for it (its conv pads k // 2 "
+                            "and returns T + 1 frames)" % (who, kernel_size))
 
 
 # ----------------------------------------------------------------------------
@@ -186,7 +195,7 @@ class PointwiseConv1d(nn.Conv1d):
 
 
 class GroupedConv1d(nn.Conv1d):
-    """Conv1d(k=21, groups=G) holder; `packed()` caches the kernel-side weight layout."""
+    """Conv1d(k, groups=G) holder; `packed()` caches the kernel-side weight layout."""
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
@@ -204,7 +213,7 @@ class GroupedConv1d(nn.Conv1d):
         """time-major [B, T, C_in] -> [B, T_out, C_out] (plain conv + bias, no activation)."""
         if self.stride[0] != 2 or self.padding[0] != 0:
             raise N.NativeError("GroupedConv1d.forward: only the stride-2 / pad-0 resize conv is exposed directly")
-        return ops.gconv_s2(x, self.packed(), self.bias, self.out_channels, self.groups)
+        return ops.gconv_s2(x, self.packed(), self.bias, self.out_channels, self.groups, ksize=self.kernel_size[0])
 
 
 class TDSBlock(nn.Module):
@@ -212,8 +221,7 @@ class TDSBlock(nn.Module):
 
     def __init__(self, hidden, kernel_size, groups, dropout=0.1):
         super().__init__()
-        if kernel_size != KERNEL_SIZE:
-            raise N.NativeError("TDSBlock: the HIP kernels are built for kernel_size=21")
+        _check_kernel_size("TDSBlock", kernel_size, True)
         self.conv = nn.Sequential(
             GroupedConv1d(hidden, hidden, kernel_size=kernel_size, stride=1, groups=groups,
                           padding=kernel_size // 2),
@@ -226,7 +234,7 @@ class TDSBlock(nn.Module):
     def forward_time_major(self, x):
         rw = float(self.resweight.detach())
         g = self.conv[0]
-        x = ops.gconv_res(x, g.packed(), g.bias, rw, g.groups)
+        x = ops.gconv_res(x, g.packed(), g.bias, rw, g.groups, ksize=g.kernel_size[0])
         h = ops.linear(x, self.fc[0].weight, self.fc[0].bias, mode=1)
         return ops.linear(h, self.fc[3].weight, self.fc[3].bias, mode=2, res=x, alpha=rw)
 
@@ -241,10 +249,10 @@ class TDS(nn.Module):
 
     def __init__(self, input_size, sizes, depths, kernel_size=21, dropout=0.1):
         super().__init__()
-        if kernel_size != KERNEL_SIZE:
-            raise N.NativeError("TDS: the HIP kernels are built for kernel_size=21")
+        _check_kernel_size("TDS", kernel_size, any(int(d) > 0 for d in depths))
         if len(sizes) - 1 > N.TAL_MAX_STAGES or max(depths) > N.TAL_MAX_DEPTH:
             raise N.NativeError("TDS: at most %d stages of depth %d" % (N.TAL_MAX_STAGES, N.TAL_MAX_DEPTH))
+        self.kernel_size = kernel_size
         self.extract_block_id = 1
         self.sizes = sizes
         self.depths = list(depths)
@@ -291,8 +299,11 @@ class TDS(nn.Module):
         # halves; such a layer keeps the exact fp32 kernels (no split / fragment form is built for it)
         def in_range(w):
             return bool(torch.isfinite(w).all()) and float(w.abs().max()) <= 65504.0
+        # (the fp16x3 fragments exist for k = 21 only: any other kernel size runs every grouped conv on the exact fp32 any-k kernels)
+        frags = self.kernel_size == KERNEL_SIZE
         pack = {"down_w": down.packed(),
-                "down_frag": ops.pack_gconv_f16x3_weight(down.weight.detach(), down.groups, stride=2) if in_range(down.weight.detach()) else None,
+                "down_frag": ops.pack_gconv_f16x3_weight(down.weight.detach(), down.groups, stride=2)
+                if frags and in_range(down.weight.detach()) else None,
                 "blocks": []}
         rws = torch.stack([blk.resweight.detach().reshape(()) for blk in chain]).cpu().tolist() if len(chain) else []
         for blk, rw in zip(chain, rws):
@@ -303,7 +314,7 @@ class TDS(nn.Module):
                 # form (include/tal_asrd.h), fp32-equivalent results at ~2.4x the fp32 matrix rate
                 b["fc0_split"] = ops.split_f16x3(blk.fc[0].weight.detach().reshape(c, c))
                 b["fc3_split"] = ops.split_f16x3(blk.fc[3].weight.detach().reshape(c, c))
-            if in_range(g.weight.detach()):
+            if frags and in_range(g.weight.detach()):
                 # ... and the grouped conv as fp16x3 MFMA operand fragments (widths 10 / 14 / 18 per group)
                 b["conv_frag"] = ops.pack_gconv_f16x3_weight(g.weight.detach(), g.groups)
             pack["blocks"].append(b)
@@ -321,6 +332,7 @@ class TDS(nn.Module):
         d = N.TdsDesc()
         d.n_stages = last - first
         d.groups = self.input_size
+        d.ksize = self.kernel_size
         for s in range(first, last + 1):
             d.channels[s - first] = self.sizes[s]
         for s in range(first, last):

@@ -161,7 +161,7 @@ def split_f16x3(x2d):
 
 # ------------------------------------------------------------------ grouped conv
 def pack_gconv_weight(weight, groups):
-    """reference Conv1d weight [C_out, C_in/G, 21] -> packed [G][C_in/G][21][C_out/G]."""
+    """reference Conv1d weight [C_out, C_in/G, k] -> packed [G][C_in/G][k][C_out/G] (1 <= k <= TAL_GCONV_MAX_K)."""
     lib = N.lib()
     w = _f32c(weight, "pack_gconv_weight")
     c_out, cig, ks = w.shape
@@ -171,8 +171,10 @@ def pack_gconv_weight(weight, groups):
     return packed
 
 
-def gconv_s2(x, w_packed, bias, c_out, groups):
-    """x [B, T, C_in] -> [B, (T-21)//2+1, C_out] (tal/asr/models.py:363-364)."""
+def gconv_s2(x, w_packed, bias, c_out, groups, ksize=21):
+    """x [B, T, C_in] -> [B, (T-k)//2+1, C_out] (tal/asr/models.py:363-364); k != 21 runs the any-k kernel (gconv_s2_k)."""
+    if ksize != 21:
+        return gconv_s2_k(x, w_packed, bias, c_out, groups, ksize)
     lib = N.lib()
     x = _f32c(x, "gconv_s2")
     B, T, c_in = x.shape
@@ -182,14 +184,42 @@ def gconv_s2(x, w_packed, bias, c_out, groups):
     return y
 
 
-def gconv_res(x, w_packed, bias, alpha, groups):
-    """x + alpha * relu(gconv21(x)) on [B, T, C] (tal/asr/models.py:304-308,329)."""
+def gconv_res(x, w_packed, bias, alpha, groups, ksize=21):
+    """x + alpha * relu(gconv_k(x)) on [B, T, C] (tal/asr/models.py:304-308,329); k != 21 runs the any-k kernel (gconv_res_k)."""
+    if ksize != 21:
+        return gconv_res_k(x, w_packed, bias, alpha, groups, ksize)
     lib = N.lib()
     x = _f32c(x, "gconv_res")
     B, T, c = x.shape
     y = torch.empty_like(x)
     N.check(lib.tal_gconv_res_fwd(N.ptr(x), N.ptr(w_packed), N.ptr(bias), float(alpha), B, T, c, groups, N.ptr(y),
                                   N.stream_handle()), "tal_gconv_res_fwd")
+    return y
+
+
+def gconv_s2_k(x, w_packed, bias, c_out, groups, ksize):
+    """The stride-2 resize conv at any kernel size 1..TAL_GCONV_MAX_K (tal_gconv_s2_k_fwd, exact fp32; bit-identical to
+    gconv_s2 at k = 21): x [B, T, C_in] -> [B, (T-k)//2+1, C_out]."""
+    lib = N.lib()
+    x = _f32c(x, "gconv_s2_k")
+    B, T, c_in = x.shape
+    if T < ksize:
+        raise N.NativeError("gconv_s2_k: %d frames are too few for kernel size %d" % (T, ksize))
+    y = torch.empty(B, (T - ksize) // 2 + 1, c_out, dtype=torch.float32, device=x.device)
+    N.check(lib.tal_gconv_s2_k_fwd(N.ptr(x), N.ptr(w_packed), N.ptr(bias), B, T, c_in, c_out, groups, int(ksize), N.ptr(y),
+                                   N.stream_handle()), "tal_gconv_s2_k_fwd")
+    return y
+
+
+def gconv_res_k(x, w_packed, bias, alpha, groups, ksize):
+    """x + alpha * relu(gconv_k(x)) at any odd kernel size 1..TAL_GCONV_MAX_K (tal_gconv_res_k_fwd, exact fp32; bit-identical to
+    gconv_res at k = 21)."""
+    lib = N.lib()
+    x = _f32c(x, "gconv_res_k")
+    B, T, c = x.shape
+    y = torch.empty_like(x)
+    N.check(lib.tal_gconv_res_k_fwd(N.ptr(x), N.ptr(w_packed), N.ptr(bias), float(alpha), B, T, c, groups, int(ksize), N.ptr(y),
+                                    N.stream_handle()), "tal_gconv_res_k_fwd")
     return y
 
 
@@ -324,7 +354,7 @@ def tds_forward(desc, x, c_out, check_range=True, defer=False, x_mean=None, out_
     B, T, _ = x.shape
     t_out = lib.tal_tds_out_len(C.byref(desc), T)
     if t_out <= 0:
-        raise N.NativeError("tds_forward: %d frames are too few for the stride-2 k=21 stages" % T)
+        raise N.NativeError("tds_forward: %d frames are too few for the stride-2 k=%d stages" % (T, desc.ksize or 21))
     y = torch.empty(B, t_out, c_out, dtype=torch.float32, device=x.device)
     nws = lib.tal_tds_workspace_bytes(C.byref(desc), B, T)
     ws = _ws(nws, x.device)
@@ -355,7 +385,7 @@ def tds_forward_tiled(desc, x, c_out, out_tile, check_range=True):
     T = x.shape[1]
     t_out = lib.tal_tds_out_len(C.byref(desc), T)
     if t_out <= 0:
-        raise N.NativeError("tds_forward_tiled: %d frames are too few for the stride-2 k=21 stages" % T)
+        raise N.NativeError("tds_forward_tiled: %d frames are too few for the stride-2 k=%d stages" % (T, desc.ksize or 21))
     y = torch.empty(1, t_out, c_out, dtype=torch.float32, device=x.device)
     nws = lib.tal_tds_tiled_workspace_bytes(C.byref(desc), T, int(out_tile))
     ws = _ws(nws, x.device)

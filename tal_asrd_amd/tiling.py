@@ -1,8 +1,8 @@
 """Time tiling of the TDS encoder (SURVEY §8b `halo_mode`, §8e "single hour-long clip across GPUs").
 
-The encoder (tal/asr/models.py:349-397) is a stack of stride-2 k=21 convs without padding and TDSBlocks whose k=21 conv
-pads 10 zeros at the TRUE ends of the sequence (models.py:304-308).  Output frame t therefore reads the mel frames
-[8 t - left, 8 t + right] (left = 640, right = 780 for the 2 / 3 / 6 block stack), and a slice of the sequence that
+The encoder (tal/asr/models.py:349-397) is a stack of stride-2 convs of kernel size k (21 by default) without padding and
+TDSBlocks whose conv pads k // 2 zeros at the TRUE ends of the sequence (models.py:304-308).  Output frame t therefore reads the
+mel frames [8 t - left, 8 t + right] (left = 640, right = 780 for the 2 / 3 / 6 block stack at k = 21), and a slice of the sequence that
 carries this halo reproduces the frames whose window lies inside it exactly as the whole sequence would -- the frames at
 a true end need no halo, their zero padding is the same in the slice (slices start at multiples of the total stride, so
 every stage's index 0 of the slice is a stage index of the whole).
@@ -19,12 +19,12 @@ import torch
 KERNEL_SIZE = 21
 
 
-def tds_out_len(T: int, n_stages: int = 3) -> int:
-    """Frames after the stride-2, k=21, padding-0 convs (models.py:363-364)."""
+def tds_out_len(T: int, n_stages: int = 3, kernel_size: int = KERNEL_SIZE) -> int:
+    """Frames after the stride-2, padding-0 convs of kernel size k (models.py:363-364)."""
     for _ in range(n_stages):
-        if T < KERNEL_SIZE:
+        if T < kernel_size:
             return 0
-        T = (T - KERNEL_SIZE) // 2 + 1
+        T = (T - kernel_size) // 2 + 1
     return T
 
 
@@ -49,12 +49,12 @@ class Tile:
     skip: int          # output frames of the slice's own result that precede out_start
 
 
-def plan_tiles(T: int, out_tile: int, depths: Sequence[int] = (2, 3, 6)) -> List[Tile]:
+def plan_tiles(T: int, out_tile: int, depths: Sequence[int] = (2, 3, 6), kernel_size: int = KERNEL_SIZE) -> List[Tile]:
     """Tiles of `out_tile` output frames over an input of T frames; [] if the input is shorter than one output frame."""
     if out_tile < 1:
         raise ValueError("plan_tiles: out_tile must be positive")
-    left, right, stride = receptive_halo(depths)
-    t_out = tds_out_len(T, len(list(depths)))
+    left, right, stride = receptive_halo(depths, kernel_size)
+    t_out = tds_out_len(T, len(list(depths)), kernel_size)
     tiles = []
     for o0 in range(0, t_out, out_tile):
         o1 = min(o0 + out_tile, t_out)
@@ -102,9 +102,10 @@ def encode_tiled(encoder, mel: torch.Tensor, out_tile: int, tiles: Sequence[Tile
     if mel.dim() != 3 or mel.shape[0] != 1:
         raise ValueError("encode_tiled: mel must be [1, T, C]")
     depths = tuple(encoder.depths)
+    k = getattr(encoder, "kernel_size", KERNEL_SIZE)
     T = int(mel.shape[1])
-    todo = plan_tiles(T, out_tile, depths) if tiles is None else list(tiles)
-    out = torch.zeros(1, tds_out_len(T, len(depths)), encoder.sizes[-1], dtype=torch.float32, device=mel.device)
+    todo = plan_tiles(T, out_tile, depths, k) if tiles is None else list(tiles)
+    out = torch.zeros(1, tds_out_len(T, len(depths), k), encoder.sizes[-1], dtype=torch.float32, device=mel.device)
     for t, y in encode_tiles(encoder, mel, todo, batch).items():
         out[0, t.out_start:t.out_stop] = y
     return out
