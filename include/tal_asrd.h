@@ -271,7 +271,16 @@ size_t tal_tds_workspace_bytes(const tal_tds_desc* d, int B, int64_t T);
  * kernel tracks max |x|; tal_tds_fwd clears a status word in its workspace at tal_tds_status_offset() bytes and the
  * kernels raise it (non-zero int32) when a value was out of range -- the output of that call is then NOT valid and the
  * caller re-runs it with desc->flags |= TAL_TDS_EXACT_F32 (fp32-input MFMA kernels, no range limit).  Values below
- * 2^-24 in magnitude lose their low half (absolute error <= 2^-35 per product, far below fp32 resolution of the sums).
+ * 2^-24 in magnitude lose their low half (absolute error <= 2^-35 per product, far below fp32 resolution of the sums);
+ * fp16 subnormal halves are kept by the conversions and by the MFMA inputs (measured: profiles/fp16x3_range.txt).
+ * The threshold is |x| > 65504 exactly: 65505 .. 65519 still round to 65504 in fp16 and raise the word.
+ * Values below ~2^-24 are therefore carried with few or no significant bits: the bound is absolute, not relative.
+ * Non-finite values: when a value that is turned into halves is +-Inf or NaN, either the status word is raised or the
+ * non-finite value is in the call's output; finite output under a clear word does not happen for CONVERTED data.  +-Inf
+ * always raises the word; a NaN raises it at the sites whose halves are clamped and otherwise travels on in the
+ * (unclamped) halves.  The one exception lies in front of the conversion: ReLU is fmaxf(v, 0) in every kernel of this
+ * library, the fp32 ones included, so a NaN that first appears under a ReLU (a NaN bias, say) becomes 0 and is never
+ * converted (PyTorch would keep it); a NaN in the input of the call is caught at the first converting site.
  * Stream capture: tal_logmel_*_fwd, tal_tds_fwd and tal_sd_head_fwd enqueue kernel launches on `stream` and nothing else (the
  * status word is cleared by a kernel, not a memset node), so a caller may capture them into a HIP graph once every one-off
  * build (plans, weight packs) has run eagerly; the status word is read after each replay like after each call. */
@@ -319,6 +328,11 @@ int tal_tds_tiled_fwd(const tal_tds_desc* d, const float* x, int64_t T, float* y
  * x [M, C] -> feat [M, E] = spk_embed_proj(x); logits [M, S] = spk_logit_proj(feat)
  * (logits may be NULL); ids [M] int32 = argmax over S (may be NULL; first
  * maximum wins, as torch.argmax).  workspace: tal_sd_head_workspace_bytes.
+ * ids without logits on long inputs run the arg-max GEMM in the fp16x3 form (features and spk_logit_proj.weight as hi / lo
+ * halves).  That form is under a range guard of its own, resolved on the device: a feature or logit weight beyond 65504
+ * (or not finite) raises a status word inside the workspace, and the exact fp32 arg-max kernel, enqueued behind the
+ * fp16x3 one, redoes the call when it is raised (it exits at once otherwise) -- the ids are those of the fp32 logits either
+ * way and the caller has nothing to check.  A workspace sized by an older header (64 bytes smaller) runs the fp32 kernel alone.
  * ------------------------------------------------------------------ */
 size_t tal_sd_head_workspace_bytes(int64_t M, int S);
 int tal_sd_head_fwd(const float* x, int64_t M, int C, const float* w_embed, const float* b_embed, int E,

@@ -792,7 +792,8 @@ extern "C" size_t tal_sd_head_workspace_bytes(int64_t M, int S) {
     // even when it is partly past S, hence the second term.
     // ... and behind them (a multiple of 256 on) room for the speaker-logit weights as hi / lo fp16 halves (S x 128 x 4 bytes), which
     // the A-stationary arg-max kernel multiplies in the fp16x3 form
-    const size_t partials = ((sd_head_partials_bytes(M, S) + 255) & ~(size_t)255) + (size_t)S * 128 * 4;
+    // ... and a 64-byte status block behind those: the range guard of that form (sd_head_after_feat)
+    const size_t partials = ((sd_head_partials_bytes(M, S) + 255) & ~(size_t)255) + (size_t)S * 128 * 4 + 64;
     // The same bytes serve first as K-slice scratch of the embedding layer (1440 -> 128: ONE column tile, so a clip of minutes is
     // a few dozen 128-row tiles for 256 CUs -- 120 us on 30 workgroups for a 5-minute clip; cut along K 8 ways it is ~30 us).
     // launch_gemm slices only launches below a quarter round (128 tiles).
@@ -861,14 +862,23 @@ static int sd_head_after_feat(int64_t M, int E, const float* w_logit, const floa
         // the speaker-logit weights as hi / lo fp16 split in the unused tail of the workspace (3 MB, one ~5 us pass per call):
         // the arg-max GEMM then runs in the fp16x3 form of the dense layers
         const bool head_f32 = opt(OPT_TDS_EXACT_F32) != 0;
+        // fp16-range guard of this form: the weight split and the kernel's feature split clamp, so a logit weight or a feature
+        // outside the fp16 range (or not finite) would give plausible wrong ids.  Both raise a status word behind the split
+        // weights, and the fp32 kernel is enqueued behind the fp16x3 one: it returns at once while the word is clear and redoes
+        // the whole arg-max exactly when it is raised -- no host round trip, the ids are right either way.  Without room for
+        // the word (a workspace sized by an older header) the fp32 kernel runs alone.
         void* wsplit = nullptr;
+        int* guard = nullptr;
         const size_t used = ((size_t)M * P * 8 + 255) & ~(size_t)255;
-        if (!head_f32 && E % 32 == 0 && (reinterpret_cast<uintptr_t>(w_logit) & 15) == 0 && used + (size_t)S * E * 4 <= workspace_bytes) {
+        if (!head_f32 && E % 32 == 0 && (reinterpret_cast<uintptr_t>(w_logit) & 15) == 0 && used + (size_t)S * E * 4 + 64 <= workspace_bytes) {
             wsplit = reinterpret_cast<char*>(workspace) + used;
-            rc = launch_split_f16x3(w_logit, wsplit, S, E, s);
+            guard = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + used + (size_t)S * E * 4);
+            clear_status_kernel<<<1, 16, 0, s>>>(guard);
+            TAL_CHECK_LAUNCH("tal_sd_head_fwd(status)");
+            rc = launch_split_f16x3(w_logit, wsplit, S, E, s, guard);
             if (rc) return rc;
         }
-        rc = launch_head_argmax(feat, w_logit, wsplit, b_logit, M, S, pv, pi, s);
+        rc = launch_head_argmax(feat, w_logit, wsplit, b_logit, M, S, pv, pi, s, guard);
         if (rc) return rc;
         ProfScope prof(PROF_OTHER, (double)M * P * 8.0, s);
         hipLaunchKernelGGL(argmax_partials_kernel, dim3((unsigned)cdiv(M, 4)), dim3(256), 0, s, pv, pi, M, P, P, ids);

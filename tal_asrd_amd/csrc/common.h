@@ -78,7 +78,18 @@ __device__ __forceinline__ float amax4(float a, const f32x4& v) {
     return fmaxf(fmaxf(a, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
 }
 __device__ __forceinline__ void note_range(float amax, int* flag) {
-    if (flag && amax > 65504.f) atomicOr(flag, 1);
+    if (flag && !(amax <= 65504.f)) atomicOr(flag, 1);      // (a NaN maximum raises the word too)
+}
+// fmaxf drops a NaN operand, so a maximum built from it never sees one.  That is harmless where the halves come from the
+// unclamped split_f16x3_pair (the NaN reaches the output by itself), but the clamped split_f16x3 turns a NaN into a finite
+// half: sites that clamp AND report to the status word track the maximum of |x| as a bit pattern instead -- non-negative
+// floats order like unsigned integers, and Inf / NaN patterns lie above every finite one and stick.  Same flag for finite data.
+__device__ __forceinline__ float amax_nan(float a, float v) {
+    const unsigned ua = __float_as_uint(a), uv = __float_as_uint(v) & 0x7fffffffu;
+    return __uint_as_float(ua > uv ? ua : uv);
+}
+__device__ __forceinline__ float amax4_nan(float a, const f32x4& v) {
+    return amax_nan(amax_nan(a, v.x), amax_nan(amax_nan(0.f, v.y), amax_nan(amax_nan(0.f, v.z), v.w)));
 }
 
 // The same split on a pair without clamps, for kernels that run under the fp16-range guard (an out-of-range value makes
@@ -253,7 +264,7 @@ int launch_logmel_mean(const double* partial, int64_t nparts, double count, floa
 bool head_argmax_applicable(int64_t M, int S, int E);
 int head_argmax_partials(int64_t M, int S);
 int launch_head_argmax(const float* feat, const float* w, const void* w_split, const float* b, int64_t M, int S, float* part_val,
-                       int32_t* part_idx, hipStream_t s);
+                       int32_t* part_idx, hipStream_t s, int* range_flag = nullptr);
 
 // ---- latency-oriented kernels of the decode step (csrc/decode_small.hip) ----
 struct SkinnyArgs {

@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void gconv_s2_c1_kernel(const float* __restric
             if (YSPLIT) {
                 _Float16 hi, lo;
                 split_f16x3(acc, hi, lo);
-                amax = fmaxf(amax, fabsf(acc));
+                amax = amax_nan(amax, acc);           // (clamped halves: a NaN must reach the status word)
                 const unsigned short hb = __builtin_bit_cast(unsigned short, hi), lb = __builtin_bit_cast(unsigned short, lo);
                 const unsigned mine = (unsigned)hb | ((unsigned)lb << 16);
                 const unsigned other = __shfl_xor(mine, 1, 64);
@@ -610,7 +610,7 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
                     _Float16 h0, l0, h1, l1;
                     split_f16x3(acc[0], h0, l0);
                     split_f16x3(acc[1], h1, l1);
-                    if (inside) amax = fmaxf(amax, fmaxf(fabsf(acc[0]), fabsf(acc[1])));
+                    if (inside) amax = amax_nan(amax_nan(amax, acc[0]), acc[1]);
                     const f16x2 zz = {(_Float16)0.f, (_Float16)0.f};
                     const f16x2 hh = {h0, h1}, ll = {l0, l1};
                     *reinterpret_cast<f16x2*>(dh + (r + q) * P0) = inside ? hh : zz;
@@ -704,7 +704,7 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
             for (int u = 0; u < UNR; ++u)
                 v[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, voff + (p0 + u) * RPP * C_in * 4, 0, 0));
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) amax = amax4(amax, v[u]);
+            for (int u = 0; u < UNR; ++u) amax = amax4_nan(amax, v[u]);
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const int ti = r0 + (p0 + u) * RPP;

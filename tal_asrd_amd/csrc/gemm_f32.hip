@@ -562,7 +562,7 @@ __global__ __launch_bounds__(256) void gemm_splitk_fixup_kernel(const GemmArgs g
             if (MODE == 3 && (g.scale_cols == 0 || col < g.scale_cols)) v = g.alpha * v;
             if (g.out_split) {
                 f16x4 hi, lo;
-                note_range(amax4(0.f, v), g.range_flag);
+                note_range(amax4_nan(0.f, v), g.range_flag);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     _Float16 h, l;
@@ -850,7 +850,7 @@ __global__ __launch_bounds__(256) void split_f16x3_kernel(const float* __restric
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n4) return;
     const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-    note_range(amax4(0.f, v), range_flag);
+    note_range(amax4_nan(0.f, v), range_flag);
     f16x4 hi, lo;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {

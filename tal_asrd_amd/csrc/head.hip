@@ -37,7 +37,10 @@ template <bool F16X3>
 __global__ __launch_bounds__(256, 2) void head_argmax_kernel(const float* __restrict__ feat, const float* __restrict__ W,
                                                             const float* __restrict__ bias, int64_t M, int S, int NT,
                                                             int64_t U, float* __restrict__ part_val,
-                                                            int32_t* __restrict__ part_idx, int HP) {
+                                                            int32_t* __restrict__ part_idx, int HP, int* __restrict__ range_flag) {
+    // range guard (launch_head_argmax): the fp16x3 kernel reports features outside the fp16 range; the fp32 kernel enqueued
+    // behind it runs only when the word is raised (by that kernel or by the weight split)
+    if (!F16X3 && range_flag && *range_flag == 0) return;
     __shared__ __attribute__((aligned(16))) float lds[2 * HBN * 32];   // 40,960 B
     const int64_t G = gridDim.x;
     const int64_t u0 = (int64_t)blockIdx.x * U / G, u1 = ((int64_t)blockIdx.x + 1) * U / G;
@@ -97,9 +100,11 @@ __global__ __launch_bounds__(256, 2) void head_argmax_kernel(const float* __rest
             r = r < M ? r : M - 1;
             if (F16X3) {
                 const float* ap = feat + r * HK + 8 * fhalf;
+                float amax = 0.f;
 #pragma unroll
                 for (int q = 0; q < HK / 16; ++q) {
                     const f32x4 v0 = *reinterpret_cast<const f32x4*>(ap + 16 * q), v1 = *reinterpret_cast<const f32x4*>(ap + 16 * q + 4);
+                    amax = amax4_nan(amax4_nan(amax, v0), v1);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         _Float16 h, l;
@@ -109,6 +114,7 @@ __global__ __launch_bounds__(256, 2) void head_argmax_kernel(const float* __rest
                         ah[q][4 + i] = h; al[q][4 + i] = l;
                     }
                 }
+                note_range(amax, range_flag);
             } else {
                 const float* ap = feat + r * HK + 4 * fhalf;
 #pragma unroll
@@ -267,8 +273,10 @@ int head_argmax_partials(int64_t M, int S) {
 }
 
 // w_split != nullptr: W as the hi / lo split of tal_split_f16x3_fwd -> the fp16x3 kernel; else w (fp32) -> the fp32 MFMA kernel
+// range_flag (with w_split, zero on entry or raised by the weight split): the fp16x3 kernel ORs it when a feature lies outside the
+// fp16 range, and the fp32 kernel runs behind it over the same partials when the word is raised (it exits at once otherwise)
 int launch_head_argmax(const float* feat, const float* w, const void* w_split, const float* b, int64_t M, int S, float* part_val,
-                       int32_t* part_idx, hipStream_t s) {
+                       int32_t* part_idx, hipStream_t s, int* range_flag) {
     TAL_CHECK_ARG(feat && (w || w_split) && b && part_val && part_idx, "head_argmax: null pointer");
     TAL_CHECK_ARG(((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(w_split)) & 15) == 0, "head_argmax: operands must be 16-byte aligned");
     const int NT = (int)cdiv(S, HBN);
@@ -278,11 +286,14 @@ int launch_head_argmax(const float* feat, const float* w, const void* w_split, c
     head_argmax_plan(M, S, grid, hp);
     TAL_CHECK_ARG(grid >= 1, "head_argmax: too few rows (M=%lld)", (long long)M);
     ProfScope prof(PROF_GEMM, 2.0 * (double)M * (double)S * HK, s);
-    if (w_split)
+    TAL_CHECK_ARG(!w_split || (range_flag && w), "head_argmax: the fp16x3 form needs its status word and the fp32 weights");
+    if (w_split) {
         hipLaunchKernelGGL(head_argmax_kernel<true>, dim3((unsigned)grid), dim3(256), 0, s, feat, reinterpret_cast<const float*>(w_split), b, M,
-                           S, NT, U, part_val, part_idx, hp);
-    else
-        hipLaunchKernelGGL(head_argmax_kernel<false>, dim3((unsigned)grid), dim3(256), 0, s, feat, w, b, M, S, NT, U, part_val, part_idx, hp);
+                           S, NT, U, part_val, part_idx, hp, range_flag);
+        hipLaunchKernelGGL(head_argmax_kernel<false>, dim3((unsigned)grid), dim3(256), 0, s, feat, w, b, M, S, NT, U, part_val, part_idx, hp, range_flag);
+    } else
+        hipLaunchKernelGGL(head_argmax_kernel<false>, dim3((unsigned)grid), dim3(256), 0, s, feat, w, b, M, S, NT, U, part_val, part_idx, hp,
+                           (int*)nullptr);
     TAL_CHECK_LAUNCH("head_argmax");
     return TAL_OK;
 }
