@@ -134,6 +134,37 @@ int tal_logmel_general_fwd(const void* plan, int n_fft, int hop, int n_mels, con
                            float eps, int subtract_mean, float* out, float* mean_out, double* sum_out, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------
+ * Waveform resampling (csrc/resample.hip): torchaudio 0.4.0's kaldi.resample_waveform, which the reference's loaders run on the
+ * CPU after torchaudio.load (tal/asr/data/util.py:45-48), restated.  Integer rates orig -> new_rate, lowpass_filter_width `width`
+ * (torchaudio's default: 6).  With g = gcd, iu = orig / g, ou = new_rate / g: output q * ou + p is
+ * sum_j w[p][j] * x[q * iu + first[p] + j] over `taps` terms in ascending j (fp32 FMA chain; x = 0 outside the item), with the
+ * Hann-windowed sinc table w (cutoff 0.99 * min(orig, new_rate) / 2) computed in double on the host and rounded to fp32.
+ * Limits: rates 1..2^20 Hz, width 1..64, taps <= 1024, ou * taps <= 2^20 table entries (16001 -> 16000 takes 208000),
+ * and orig / new_rate small enough that 64 outputs' input span fits the 24 KiB staging buffer (about 80 at width 6).
+ * ------------------------------------------------------------------ */
+#define TAL_RESAMPLE_F32 0
+#define TAL_RESAMPLE_F16 1
+#define TAL_RESAMPLE_I16 2   /* 16-bit PCM, scaled by 2^-15 as torchaudio.load does */
+/* samples out for n_in samples in: the output instants m / new_rate < n_in / orig (0 for n_in <= 0 or a rate < 1).  Host code. */
+int64_t tal_resample_num_samples(int64_t n_in, int orig, int new_rate);
+/* bytes of a plan; 0 outside the limits above. */
+size_t tal_resample_plan_bytes(int orig, int new_rate, int width);
+/* the table on the host (no GPU involved): *taps, first [ou] and w [ou][taps]; w and first may be NULL (call once for taps, then
+ * again with the buffers).  TAL_EINVAL with a message that names the limit outside the limits. */
+int tal_resample_plan_build_host(int orig, int new_rate, int width, float* w, int32_t* first, int* taps);
+/* build the plan in device memory of tal_resample_plan_bytes bytes; one-time, synchronises `stream`. */
+int tal_resample_plan_init(void* plan, int orig, int new_rate, int width, void* stream);
+/* x [B, L_in] (rows x_pitch elements apart; x_dtype = TAL_RESAMPLE_*: fp16 and int16 samples are widened exactly while they are
+ * staged, so the result equals the fp32 call on the widened samples bit for bit) -> y fp32 [B, n_out(L_in)] (rows y_pitch floats
+ * apart).  orig / new_rate / width are the plan's (the host keeps them; a plan built for another pair makes the outputs NaN).
+ * lengths (device, int64 [B], or NULL): input at or beyond lengths[b] reads as zero and output at or beyond n_out(lengths[b]) is
+ * written as zero -- resample, then right-pad.  Every output is a function of its phase and its taps input samples alone: results
+ * do not depend on B, on the item's position in the batch or on timing.  Sample offsets are 64-bit (B * L_in may exceed 2^31).
+ * Enqueues one launch: no allocation, no synchronisation. */
+int tal_resample_fwd(const void* plan, int orig, int new_rate, int width, const void* x, int x_dtype, int B, int64_t L_in,
+                     int64_t x_pitch, const int64_t* lengths, float* y, int64_t y_pitch, void* stream);
+
 /* ------------------------------------------------------------------ *
  * Dense layer: y = epilogue(x . W^T + b), nn.Linear / 1x1 Conv1d.
  * x [M, K] row-major (ld = K), W [N, K] row-major (the nn.Linear /

@@ -86,6 +86,11 @@ SIGNATURES = {
     "tal_logmel_general_plan_init": (_i, [_p, _i, _i, _p, _i, _p, _p]),
     "tal_logmel_general_workspace_bytes": (_sz, [_i, _i, _i, _i64]),
     "tal_logmel_general_fwd": (_i, [_p, _i, _i, _i, _p, _i, _i, _i64, _f, _i, _p, _p, _p, _p, _sz, _p]),
+    "tal_resample_num_samples": (_i64, [_i64, _i, _i]),
+    "tal_resample_plan_bytes": (_sz, [_i, _i, _i]),
+    "tal_resample_plan_build_host": (_i, [_i, _i, _i, _p, _p, C.POINTER(C.c_int)]),
+    "tal_resample_plan_init": (_i, [_p, _i, _i, _i, _p]),
+    "tal_resample_fwd": (_i, [_p, _i, _i, _i, _p, _i, _i, _i64, _i64, _p, _p, _i64, _p]),
     "tal_linear_fwd": (_i, [_p, _p, _p, _p, _f, _i, _i64, _i, _i, _p, _p]),
     "tal_linear_workspace_bytes": (_sz, [_i64, _i, _i]),
     "tal_split_f16x3_fwd": (_i, [_p, _p, _i64, _i, _p]),

@@ -7,6 +7,9 @@ checkpoint loading work unchanged:
 
     LogMelSpec, TDSBlock, TDS, SDModel, ASRModel, ModRZTXDecoderLayer
 
+plus `Resample` (torchaudio.transforms.Resample's constructor and call shape: the step the reference's loaders run on the CPU,
+tal/asr/data/util.py:45-48) and the `sample_rate=` argument of the models' waveform entry points that runs it on the device.
+
 Differences that are deliberate and documented in DESIGN.md:
   * inference only: dropout / SpecAugment (models.py:531-566) are not built;
   * activations are time-major [B, T, C] inside; `TDS.forward` keeps the
@@ -154,6 +157,7 @@ class LogMelSpec(nn.Module):
         self.mel_transform = MelSpectrogram(sample_rate=sr, n_mels=n_mels, n_fft=int(25 / 1000 * sr),
                                             win_length=int(25 / 1000 * sr), hop_length=int(10 / 1000 * sr))
         self.eps = eps
+        self.sample_rate = sr
         self._plan = None
         self._plan_key = None
 
@@ -177,6 +181,61 @@ class LogMelSpec(nn.Module):
         N.require_cuda(audio, "LogMelSpec.forward_unsubtracted")
         out, mean, _ = ops.logmel(self.plan(), audio, eps=self.eps, subtract_mean=False, return_stats=True)
         return out, mean
+
+
+class Resample(nn.Module):
+    """torchaudio.transforms.Resample(orig_freq, new_freq) (0.4.0: kaldi.resample_waveform with lowpass_filter_width 6, restated in
+    csrc/resample.hip) on the device: waveform [..., L] fp32, fp16 or int16 (16-bit PCM as it sits in a file, scaled by 2^-15 as
+    torchaudio.load does) -> fp32 [..., n_out(L)].  No parameters and no buffers: the filter table is a device plan built on first
+    use per device.  orig_freq == new_freq runs the one-phase filter the formula gives, as torchaudio 0.4.0 does."""
+
+    def __init__(self, orig_freq=DEFAULT_SR, new_freq=DEFAULT_SR):
+        super().__init__()
+        ops.resample_plan_bytes(orig_freq, new_freq)        # (raises outside the kernel's limits, naming the limit)
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self._plans = {}
+
+    def plan(self, device):
+        if device not in self._plans:
+            self._plans[device] = ops.resample_plan(self.orig_freq, self.new_freq, device)
+        return self._plans[device]
+
+    def num_samples(self, n_in):
+        """n_out: samples out for n_in samples in (an int, or a tensor of lengths such as audio_lens)."""
+        return ops.resample_num_samples(n_in, self.orig_freq, self.new_freq)
+
+    @torch.no_grad()
+    def forward(self, waveform: torch.Tensor, lengths=None):
+        """lengths (one per row, in input samples): rows are resampled as if cut there and right-padded with zeros afterwards."""
+        N.require_cuda(waveform, "Resample.forward")
+        return ops.resample(self.plan(waveform.device), waveform, lengths=lengths)
+
+    def extra_repr(self):
+        return "orig_freq=%d, new_freq=%d" % (self.orig_freq, self.new_freq)
+
+
+class _Resampled:
+    """`sample_rate=` of the models' entry points: resamplers by source rate, kept outside the module tree (plain dict: no new
+    submodule, state_dict key or parameter-registration event)."""
+
+    def _resampler(self, sample_rate):
+        """None where the waveform already is at the model's rate (sample_rate None or equal: the call is today's, untouched)."""
+        own = self.logmelspec.sample_rate
+        if sample_rate is None or sample_rate == own:
+            return None
+        cache = self.__dict__.setdefault("_resamplers", {})
+        if sample_rate not in cache:
+            cache[sample_rate] = Resample(sample_rate, own)
+        return cache[sample_rate]
+
+    def _resample_batch(self, x, audio_lens, sample_rate):
+        """-> (x at the model's rate, audio_lens in its samples); rows are zero from their own resampled length on."""
+        rs = self._resampler(sample_rate)
+        if rs is None:
+            return x, audio_lens
+        if audio_lens is None:
+            return rs(x), None
+        return rs(x, lengths=audio_lens), rs.num_samples(audio_lens)
 
 
 # ----------------------------------------------------------------------------
@@ -428,7 +487,7 @@ def _check_encoder_mels(n_mels, who):
                             "(n_mels must be even)" % (who, n_mels, 10 * n_mels))
 
 
-class SDModel(nn.Module):
+class SDModel(_Resampled, nn.Module):
     """Separate-diarizer baseline (tal/asr/models.py:400-485)."""
 
     def __init__(self, num_speakers=6008, n_mels=80, dropout=0.2, embed_size=128):
@@ -451,12 +510,18 @@ class SDModel(nn.Module):
     def extract_features(self, x, specaug=True):
         return self.logmelspec(x)
 
-    def encode_features(self, x: torch.Tensor, audio_lens: torch.LongTensor = None):
+    def encode_features(self, x: torch.Tensor, audio_lens: torch.LongTensor = None, sample_rate=None):
+        """sample_rate: the rate audio_lens is counted at when it is not the model's (the features are the resampled waveform's)."""
+        rs = self._resampler(sample_rate)
+        if rs is not None and audio_lens is not None:
+            audio_lens = rs.num_samples(audio_lens)
         x = self.encoder.forward_time_major(x)
         mask = None if audio_lens is None else padding_mask(audio_lens, x.size(1), x.device)
         return {"encoder_out": x, "encoder_padding_mask": mask}
 
-    def encode(self, x: torch.Tensor, audio_lens: torch.LongTensor = None):
+    def encode(self, x: torch.Tensor, audio_lens: torch.LongTensor = None, sample_rate=None):
+        """sample_rate: x (fp32 / fp16 / int16 PCM) and audio_lens are at this rate; x is resampled on the device first."""
+        x, audio_lens = self._resample_batch(x, audio_lens, sample_rate)
         return self.encode_features(self.extract_features(x), audio_lens)
 
     def decode(self, encoder_out, past=None, causal_mask=True):
@@ -470,10 +535,15 @@ class SDModel(nn.Module):
         return self.decode(encoder_out), encoder_out
 
     @torch.no_grad()
-    def speaker_ids(self, x_wav, want_logits=False):
+    def speaker_ids(self, x_wav, want_logits=False, sample_rate=None):
         """The fused form of tal/baseline/reconcile.py:76-85 (get_speaker_ids): whole-episode
         waveform [1, L] -> (feat [T', 128], ids [T'] int32[, logits]) without materialising
-        the [T', 6008] logits unless asked."""
+        the [T', 6008] logits unless asked.
+        sample_rate: the waveform's rate when it is not the model's; it may then be int16 PCM, and is resampled on the device
+        (Resample, same stream) before the unchanged path below."""
+        rs = self._resampler(sample_rate)
+        if rs is not None:
+            x_wav = rs(x_wav)
         mel, mean = self.logmelspec.forward_unsubtracted(x_wav)
         return self.speaker_ids_from_logmel(mel, mean, want_logits=want_logits)
 
@@ -505,13 +575,16 @@ class SDModel(nn.Module):
         return self._embed_split_t
 
     @torch.no_grad()
-    def speaker_ids_stream(self, host_clips):
+    def speaker_ids_stream(self, host_clips, sample_rate=None):
         """The loop of tal/baseline/reconcile.py:96-102 (one episode after the other: load, `.cuda()`, get_speaker_ids) over
         waveforms held in host memory, with the upload of episode i + 1 on a copy stream under the compute of episode i:
         `host_clips` = iterable of [1, L] float32 (or float16) tensors (pinned memory for a truly asynchronous copy); yields
         (feat, ids) per clip, in order.  With ~230 MB per hour of audio and ~50 GB/s of PCIe the copy (4.5 ms) hides
-        entirely behind the 18 ms of compute."""
+        entirely behind the 18 ms of compute.
+        sample_rate: the clips' rate when it is not the model's; they may then be int16 PCM (half the upload of fp32) and each is
+        resampled on the device, on the compute stream, before its speaker_ids call."""
         dev = self.spk_embed_proj.weight.device
+        taken = (torch.float32, torch.float16) + ((torch.int16,) if self._resampler(sample_rate) is not None else ())
         copy_stream = torch.cuda.Stream(device=dev)
         compute = torch.cuda.current_stream(dev)
         # exactly two device buffers (slot 0 / 1), flat and grow-only: sized to the longest clip seen so far, a clip lands in a
@@ -522,8 +595,9 @@ class SDModel(nn.Module):
         bufs, free_ev = self._stream_bufs, [None, None]
 
         def upload(clip, slot):
-            if clip.dtype not in (torch.float32, torch.float16):
-                raise N.NativeError("speaker_ids_stream: clips must be float32 or float16 waveforms, got %s" % clip.dtype)
+            if clip.dtype not in taken:
+                raise N.NativeError("speaker_ids_stream: clips must be float32 or float16 waveforms (or int16 PCM together with "
+                                    "sample_rate=), got %s" % clip.dtype)
             nbytes = clip.numel() * clip.element_size()
             if bufs[slot] is None or bufs[slot].numel() < nbytes:
                 if free_ev[slot] is not None:
@@ -552,7 +626,7 @@ class SDModel(nn.Module):
             nxt = next(it, None)
             pending = upload(nxt, (i + 1) & 1) if nxt is not None else None
             compute.wait_event(done)
-            out = self.speaker_ids(x)
+            out = self.speaker_ids(x, sample_rate=sample_rate)
             ev = torch.cuda.Event()
             ev.record(compute)
             free_ev[slot] = ev
@@ -589,7 +663,7 @@ class ModRZTXDecoderLayer(nn.Module):
                                      memory_key_padding_mask)
 
 
-class ASRModel(nn.Module):
+class ASRModel(_Resampled, nn.Module):
     """Joint ASR + speaker model (tal/asr/models.py:56-295)."""
 
     def __init__(self, model_type="2x", num_speakers=0, n_mels=80, vocab_size=10000, n_head=4, max_positions=512,
@@ -638,7 +712,12 @@ class ASRModel(nn.Module):
     def extract_features(self, x, specaug=True):
         return self.logmelspec(x)
 
-    def encode_features(self, x: torch.Tensor, audio_lens: torch.LongTensor = None):
+    def encode_features(self, x: torch.Tensor, audio_lens: torch.LongTensor = None, sample_rate=None):
+        """sample_rate: the rate audio_lens is counted at when it is not the model's (the features are the resampled waveform's)."""
+        rs = self._resampler(sample_rate)
+        if rs is not None and audio_lens is not None:
+            audio_lens = rs.num_samples(audio_lens)
+
         def proj(e):
             spk = ops.linear(e, self.spk_enc_proj.weight, self.spk_enc_proj.bias) if self.use_speaker_head else None
             return spk, ops.linear(e, self.decoder_proj.weight, self.decoder_proj.bias)
@@ -646,7 +725,9 @@ class ASRModel(nn.Module):
         mask = None if audio_lens is None else padding_mask(audio_lens, x.size(1), x.device)
         return {"speaker_out": spk_h, "encoder_out": x, "encoder_padding_mask": mask}
 
-    def encode(self, x: torch.Tensor, audio_lens: torch.LongTensor = None):
+    def encode(self, x: torch.Tensor, audio_lens: torch.LongTensor = None, sample_rate=None):
+        """sample_rate: x (fp32 / fp16 / int16 PCM) and audio_lens are at this rate; x is resampled on the device first."""
+        x, audio_lens = self._resample_batch(x, audio_lens, sample_rate)
         return self.encode_features(self.extract_features(x), audio_lens)
 
     def decode(self, y_prev, encoder_out, past=None, causal_mask=True):

@@ -78,7 +78,9 @@ def _audio(t, what):
     are (the kernel widens fp16 samples while it stages them); anything else raises."""
     N.require_cuda(t, what)
     if t.dtype not in (torch.float32, torch.float16):
-        raise N.NativeError("%s: the waveform must be float32 or float16, got %s" % (what, t.dtype))
+        raise N.NativeError("%s: the waveform must be float32 or float16, got %s%s" % (what, t.dtype, (
+            " (16-bit PCM goes through tal_asrd_amd.Resample(orig_freq, new_freq), or the sample_rate= argument of the models' "
+            "entry points, which scale it by 2^-15 on the device)") if t.dtype == torch.int16 else ""))
     return t.contiguous()
 
 
@@ -118,6 +120,97 @@ def subtract_scalar_(x, mean):
     lib = N.lib()
     N.check(lib.tal_subtract_scalar(N.ptr(x), x.numel(), N.ptr(mean), N.stream_handle()), "tal_subtract_scalar")
     return x
+
+
+# ------------------------------------------------------------------ resampling
+RESAMPLE_WIDTH = 6        # torchaudio's lowpass_filter_width default, the only one the reference uses
+_RESAMPLE_DTYPES = {torch.float32: 0, torch.float16: 1, torch.int16: 2}     # TAL_RESAMPLE_F32 / _F16 / _I16
+
+
+class ResamplePlan:
+    """Device table of one rate pair (tal_resample_plan_init) with the pair it was built for."""
+
+    def __init__(self, buf, orig, new, width):
+        self.buf, self.orig, self.new, self.width = buf, orig, new, width
+
+    @property
+    def device(self):
+        return self.buf.device
+
+
+def _rate(v, what):
+    if isinstance(v, bool) or int(v) != v:
+        raise N.NativeError("%s: sample rates are integers (Hz), got %r" % (what, v))
+    return int(v)
+
+
+def resample_plan_bytes(orig, new, width=RESAMPLE_WIDTH):
+    """Bytes of the pair's device plan; raises with the violated limit outside the limits (host arithmetic, no GPU)."""
+    lib = N.lib()
+    orig, new = _rate(orig, "resample_plan"), _rate(new, "resample_plan")
+    if max(abs(orig), abs(new)) >= 2 ** 31:
+        raise N.NativeError("resample_plan(%d -> %d): sample rates must be 1..1048576 Hz" % (orig, new))
+    nbytes = lib.tal_resample_plan_bytes(orig, new, width)
+    if nbytes == 0:
+        # the host builder's message names the limit that is violated
+        N.check(lib.tal_resample_plan_build_host(orig, new, width, None, None, None), "resample_plan(%d -> %d)" % (orig, new))
+        raise N.NativeError("resample_plan(%d -> %d): outside the plan limits" % (orig, new))
+    return nbytes
+
+
+def resample_plan(orig, new, device, width=RESAMPLE_WIDTH):
+    lib = N.lib()
+    nbytes = resample_plan_bytes(orig, new, width)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise N.NativeError("resample_plan: the hot path only runs on the GPU (HIP kernels); got device %s and there is deliberately "
+                            "no CPU fallback" % device)
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        N.check(lib.tal_resample_plan_init(N.ptr(buf), int(orig), int(new), width, N.stream_handle()), "tal_resample_plan_init")
+    return ResamplePlan(buf, int(orig), int(new), width)
+
+
+def resample_num_samples(n_in, orig, new):
+    """Samples out for n_in samples in (an int, or an integer tensor mapped element by element on the host, as audio_lens)."""
+    lib = N.lib()
+    orig, new = _rate(orig, "resample_num_samples"), _rate(new, "resample_num_samples")
+    if isinstance(n_in, torch.Tensor):
+        flat = [lib.tal_resample_num_samples(int(v), orig, new) for v in n_in.detach().cpu().reshape(-1).tolist()]
+        return torch.tensor(flat, dtype=torch.int64).reshape(n_in.shape)
+    return lib.tal_resample_num_samples(int(n_in), orig, new)
+
+
+def resample(plan, x, lengths=None):
+    """x [..., L] fp32 / fp16 / int16 (16-bit PCM, scaled by 2^-15) -> fp32 [..., n_out(L)] at plan.new Hz (tal_resample_fwd).
+    lengths (one per row of x, in input samples): input at or beyond it reads as zero, output at or beyond n_out(length) is zero."""
+    lib = N.lib()
+    N.require_cuda(x, "resample")
+    if x.dtype not in _RESAMPLE_DTYPES:
+        raise N.NativeError("resample: the waveform must be float32, float16 or int16, got %s" % x.dtype)
+    if x.dim() < 1:
+        raise N.NativeError("resample: the waveform must be [..., samples]")
+    if x.device != plan.device:
+        raise N.NativeError("resample: the plan lives on %s, the waveform on %s" % (plan.device, x.device))
+    L = x.shape[-1]
+    lead = tuple(x.shape[:-1])
+    n = lib.tal_resample_num_samples(L, plan.orig, plan.new)
+    if not (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= L) and not x.is_contiguous():
+        x = x.contiguous()
+    B = 1
+    for d in lead:
+        B *= d
+    pitch = x.stride(0) if x.dim() == 2 and B > 1 else L      # (rows of a 2-D view may be further apart than L)
+    y = torch.empty(lead + (n,), dtype=torch.float32, device=x.device)
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths).to(device=x.device, dtype=torch.int64).contiguous()
+        if lengths.numel() != B:
+            raise N.NativeError("resample: %d lengths for %d rows" % (lengths.numel(), B))
+    if B == 0 or n == 0:
+        return y
+    N.check(lib.tal_resample_fwd(N.ptr(plan.buf), plan.orig, plan.new, plan.width, N.ptr(x), _RESAMPLE_DTYPES[x.dtype], B, L, pitch,
+                                 N.ptr(lengths), N.ptr(y), n, N.stream_handle()), "tal_resample_fwd")
+    return y
 
 
 # ------------------------------------------------------------------ dense
