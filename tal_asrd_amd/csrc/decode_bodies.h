@@ -819,6 +819,127 @@ __device__ __forceinline__ void lm_pick_body(const LmPickArgs& q, const float* _
         if (tid == 0) __hip_atomic_store(reinterpret_cast<unsigned*>(out + 1 + S), host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
+#define TAL_HD __host__ __device__ __forceinline__
+TAL_HD LmPickArgs lm_pick_args(const float* h_last, const float* attn, int64_t layer_stride, int64_t head_stride, int S, float* partial,
+                               unsigned* tickets, float* out, int64_t* token_out, unsigned host_seq, const float* bias) {
+    LmPickArgs q = {};
+    q.h = h_last; q.attn = attn; q.layer_stride = layer_stride; q.head_stride = head_stride; q.S = S;
+    q.partial = partial; q.ticket_word = tickets + (TAL_GREEDY_TICKETS - 1);
+    q.out = out; q.token_out = token_out; q.host_seq = host_seq; q.bias = bias;
+    return q;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The ARGUMENTS of a decoder layer's phases on the latency-oriented kernels, built in one place for all three launch forms: the launch
+// chain and the merged step (host: csrc/decoder.hip) and the one-launch step (device: csrc/decode_persist.hip) call the same
+// builder per phase, so "the same bodies on the same arguments" -- the bit-identity of the forms -- holds by construction.
+// Phases: sa_qkv -> sa_attn -> {sa_out -> ca_q | fold_sa} -> ca_attn -> {ca_out -> ff1 | fold_ca} -> ff2.
+// Folded form (tal_decoder_layer_w.fold_*): the self-attention's out-projection + ReZero and the cross-attention's q projection are
+// ONE dense layer over [ctx | tgt] (x1 | q_c side by side in y3), and so are the cross-attention's out-projection + ReZero and
+// FFN-1 over [ctx2 | x1] (x2 | ff in y5): 6 dependent launches per layer instead of 8.
+TAL_HD int64_t pad4(int64_t n) { return (n + 3) & ~(int64_t)3; }
+TAL_HD SkinnyArgs skinny(const float* A, int64_t lda, const float* W, const float* bias, const float* res, float* Y, int64_t ldy,
+                         int M, int N, int K, float alpha) {
+    SkinnyArgs g = {};
+    g.A = A; g.W = W; g.bias = bias; g.res = res; g.Y = Y;
+    g.M = M; g.N = N; g.K = K;
+    g.lda = lda; g.ldw = K; g.ldy = ldy; g.ldres = ldy;
+    g.alpha = alpha;
+    return g;
+}
+struct LayerDims {
+    int E, H, FF;
+    float qscale;            // head_dim^-0.5, computed on the host
+};
+// one problem's (one session's) view of a layer
+struct LayerIo {
+    const float* tgt;        // [B, U, E]
+    float* out;
+    int B, U, S;
+    float *qkv, *vt, *ctx, *x1, *x2, *ff;      // qkv [B U][3E]: the v columns of it are never written (V goes out transposed into vt)
+    float *y3, *y5;          // folded layer: x1 | q_c [B U][2E] and x2 | ff [B U][E + FF]
+    const float* ck;         // cached K / V^T of the encoder window
+    int64_t k_pitch;         // floats between the window's K rows when it is a view of an episode-wide K | V table (0: E)
+    const float* cvt;
+    const uint8_t* kpm;
+    const float* tgt_mask;
+    float* probs;            // per-head cross-attention probabilities of the rows >= prob_row0, or NULL
+    int prob_row0;
+    float* sk_part;          // scratch of the kernels that merge partial results in-launch, or NULL
+    unsigned* tickets;
+};
+// q | k | v^T in one launch (q scaled; v goes out transposed per batch item WITH its bias, which is part of the packed bias:
+// P . (V + b) = P . V + b because rows of P sum to 1)
+TAL_HD SkinnyArgs sa_qkv(const tal_decoder_layer_w& w, const LayerIo& x, const LayerDims& d) {
+    const int E = d.E;
+    const int64_t U4 = pad4(x.U);
+    SkinnyArgs g = skinny(x.tgt, E, w.sa_in_w, w.sa_in_b, nullptr, x.qkv, 3 * E, x.B * x.U, 3 * E, E, d.qscale);
+    g.scale_cols = E;
+    g.Yt = x.vt; g.vt_begin = 2 * E; g.U = x.U; g.ldt = U4; g.vt_bs = (int64_t)E * U4;
+    return g;
+}
+// q rows of pitch ldq against k rows of pitch ldk and V^T rows of pitch pad4(S)
+TAL_HD AttnArgs attn_args(const LayerIo& x, const LayerDims& d, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* vt, int S) {
+    AttnArgs a = {};
+    a.q = q; a.ldq = ldq; a.q_bs = (int64_t)x.U * ldq;
+    a.k = k; a.ldk = ldk; a.k_bs = (int64_t)S * ldk;
+    a.vt = vt; a.ldvt = pad4(S); a.vt_bs = (int64_t)d.E * a.ldvt;
+    a.ctx = x.ctx; a.ldc = d.E; a.c_bs = (int64_t)x.U * d.E;
+    a.U = x.U; a.S = S; a.H = d.H;
+    return a;
+}
+TAL_HD AttnArgs sa_attn(const LayerIo& x, const LayerDims& d) {
+    AttnArgs a = attn_args(x, d, x.qkv, 3 * d.E, x.qkv + d.E, 3 * d.E, x.vt, x.U);
+    a.mask = x.tgt_mask;
+    return a;
+}
+TAL_HD SkinnyArgs sa_out(const tal_decoder_layer_w& w, const LayerIo& x, const LayerDims& d) {
+    return skinny(x.ctx, d.E, w.sa_out_w, w.sa_out_b, x.tgt, x.x1, d.E, x.B * x.U, d.E, d.E, w.resweight);
+}
+TAL_HD SkinnyArgs ca_q(const tal_decoder_layer_w& w, const LayerIo& x, const LayerDims& d) {
+    return skinny(x.x1, d.E, w.ca_in_w, w.ca_in_b, nullptr, x.qkv, d.E, x.B * x.U, d.E, d.E, d.qscale);
+}
+TAL_HD SkinnyArgs fold_sa(const tal_decoder_layer_w& w, const LayerIo& x, const LayerDims& d) {
+    const int E = d.E;
+    SkinnyArgs g = skinny(x.ctx, E, w.fold_sa_w, w.fold_sa_b, nullptr, x.y3, 2 * E, x.B * x.U, 2 * E, 2 * E, 0.f);
+    g.A2 = x.tgt; g.lda2 = E; g.K1 = E; g.k1_cols = E;
+    return g;
+}
+// cross attention over the cached K / V^T of the encoder window (the v bias is added after P.V)
+TAL_HD AttnArgs ca_attn(const tal_decoder_layer_w& w, const LayerIo& x, const LayerDims& d, bool fold) {
+    const int E = d.E;
+    AttnArgs c = attn_args(x, d, fold ? x.y3 + E : x.qkv, fold ? 2 * E : E, x.ck, x.k_pitch ? x.k_pitch : E, x.cvt, x.S);
+    c.vbias = w.ca_in_b + 2 * E;
+    c.kpm = x.kpm;
+    c.probs = x.probs; c.prob_row0 = x.prob_row0;
+    return c;
+}
+TAL_HD SkinnyArgs ca_out(const tal_decoder_layer_w& w, const LayerIo& x, const LayerDims& d) {
+    return skinny(x.ctx, d.E, w.ca_out_w, w.ca_out_b, x.x1, x.x2, d.E, x.B * x.U, d.E, d.E, w.resweight_src);
+}
+TAL_HD SkinnyArgs ff1(const tal_decoder_layer_w& w, const LayerIo& x, const LayerDims& d) {
+    return skinny(x.x2, d.E, w.lin1_w, w.lin1_b, nullptr, x.ff, d.FF, x.B * x.U, d.FF, d.E, 0.f);
+}
+TAL_HD SkinnyArgs fold_ca(const tal_decoder_layer_w& w, const LayerIo& x, const LayerDims& d) {
+    const int E = d.E, FF = d.FF;
+    SkinnyArgs g = skinny(x.ctx, E, w.fold_ca_w, w.fold_ca_b, nullptr, x.y5, E + FF, x.B * x.U, E + FF, 2 * E, 0.f);
+    g.A2 = x.y3; g.lda2 = 2 * E; g.K1 = E; g.k1_cols = E;          // x1 = the first E columns of y3
+    g.relu_begin = E;                                             // x2 plain, ff through the relu
+    return g;
+}
+// ksplit (K = FF is deep): four workgroups per tile, each pulling a quarter of the operands (tickets 64 .. 254)
+TAL_HD SkinnyArgs ff2(const tal_decoder_layer_w& w, const LayerIo& x, const LayerDims& d, bool fold, bool ksplit) {
+    const int E = d.E, FF = d.FF;
+    SkinnyArgs g = fold ? skinny(x.y5 + E, E + FF, w.lin2_w, w.lin2_b, x.y5, x.out, E, x.B * x.U, E, FF, w.resweight)
+                        : skinny(x.ff, FF, w.lin2_w, w.lin2_b, x.x2, x.out, E, x.B * x.U, E, FF, w.resweight);
+    if (fold) g.ldres = E + FF;
+    if (ksplit) {
+        g.ksplit = 4;
+        g.sk_part = x.sk_part;
+        g.sk_tickets = x.tickets + 64;
+    }
+    return g;
+}
 
 
 }  // namespace tal

@@ -17,17 +17,6 @@
 
 namespace tal {
 
-// (host-side mirror in decoder.hip fills these; everything by value in the kernel argument segment: <= 4 KB)
-__device__ __forceinline__ SkinnyArgs ps_skinny_args(const float* A, int64_t lda, const float* W, const float* bias, const float* res, float* Y,
-                                                     int64_t ldy, int M, int N, int K, float alpha) {
-    SkinnyArgs g = {};
-    g.A = A; g.W = W; g.bias = bias; g.res = res; g.Y = Y;
-    g.M = M; g.N = N; g.K = K;
-    g.lda = lda; g.ldw = K; g.ldy = ldy; g.ldres = ldy;
-    g.alpha = alpha;
-    return g;
-}
-
 // (ablation build -DPS_TIMELINE: workgroups 0 and G - 1 of session 0 stamp the 100 MHz wall clock around every phase barrier;
 //  scripts/decode_persist_timeline.py reads them through tal_debug_ps_timeline.  Not part of the product library.)
 #ifdef PS_TIMELINE
@@ -114,15 +103,25 @@ __device__ __forceinline__ void ps_skinny(const SkinnyArgs& g, unsigned wg, unsi
     }
 }
 
+// a session's view of layer l (batch 1, no target mask, the last row's per-head probabilities; no folded-layer buffers)
+__device__ __forceinline__ LayerIo ps_layer_io(const PsSession& s, int l, const float* cur, int H) {
+    LayerIo x = {};
+    x.tgt = cur; x.out = s.h1; x.B = 1; x.U = s.U; x.S = s.S;
+    x.qkv = s.qkv; x.vt = s.vt; x.ctx = s.ctx; x.x1 = s.x1; x.x2 = s.x2; x.ff = s.ff;
+    x.ck = s.k_cache[l]; x.k_pitch = s.k_pitch; x.cvt = s.vt_cache[l]; x.kpm = s.kpm;
+    x.probs = s.probs + (size_t)l * H * s.S; x.prob_row0 = s.U - 1;
+    x.sk_part = s.sk_part; x.tickets = s.tickets;
+    return x;
+}
+
 template <int HD>
 __global__ __launch_bounds__(256) void greedy_persist_kernel(const PsArgs a) {
     const unsigned G = (unsigned)a.G;
     const unsigned si = blockIdx.x / G, wg = blockIdx.x - si * G;
     const PsSession& s = a.s[si];
     const PsModel& m = a.m;
-    const int E = m.E, H = m.H, FF = m.FF, U = s.U, S = s.S, K0 = m.K0;
-    const int64_t U4 = (U + 3) & ~3, S4 = (S + 3) & ~3;
-    const float qscale = m.qscale;
+    const int E = m.E, H = m.H, U = s.U, S = s.S, K0 = m.K0;
+    const LayerDims d{E, H, m.FF, m.qscale};
     PsBarrier bar{s.tickets + PS_BAR, s.tickets + PS_ERR, G, 0u, si == 0 ? (wg == 0 ? 0 : (wg == G - 1 ? 1 : -1)) : -1, s.out, S, s.host_seq, wg == 0};
 
     // ---- embed (models.py:218-223)
@@ -132,24 +131,15 @@ __global__ __launch_bounds__(256) void greedy_persist_kernel(const PsArgs a) {
     }
     if (!ps_sync(bar)) return;
 
+    // ---- the UNFOLDED layer's phases, each on the arguments the launch chain builds (csrc/decode_bodies.h)
     const float* cur = s.h0;
     for (int l = 0; l < m.n_layers; ++l) {
         const tal_decoder_layer_w& w = m.layer[l];
-        // q | k | v^T of the self-attention (q scaled, V stored transposed with its bias)
-        {
-            SkinnyArgs g = ps_skinny_args(cur, E, w.sa_in_w, w.sa_in_b, nullptr, s.qkv, 3 * E, U, 3 * E, E, qscale);
-            g.scale_cols = E;
-            g.Yt = s.vt; g.vt_begin = 2 * E; g.U = U; g.ldt = U4; g.vt_bs = (int64_t)E * U4;
-            ps_skinny<3>(g, wg, G);
-        }
+        const LayerIo x = ps_layer_io(s, l, cur, H);
+        ps_skinny<3>(sa_qkv(w, x, d), wg, G);
         if (!ps_sync(bar)) return;
         {
-            AttnArgs t = {};
-            t.q = s.qkv; t.ldq = 3 * E; t.q_bs = (int64_t)U * 3 * E;
-            t.k = s.qkv + E; t.ldk = 3 * E; t.k_bs = (int64_t)U * 3 * E;
-            t.vt = s.vt; t.ldvt = U4; t.vt_bs = (int64_t)E * U4;
-            t.ctx = s.ctx; t.ldc = E; t.c_bs = (int64_t)U * E;
-            t.U = U; t.S = U; t.H = H;
+            const AttnArgs t = sa_attn(x, d);
             const unsigned gx = (unsigned)((U + 15) / 16);
             for (unsigned vb = wg; vb < gx * (unsigned)H; vb += G) {
                 attn_small_body<HD, 4, true>(t, Blk{vb % gx, vb / gx, 0u, gx, (unsigned)H});
@@ -157,58 +147,33 @@ __global__ __launch_bounds__(256) void greedy_persist_kernel(const PsArgs a) {
             }
         }
         if (!ps_sync(bar)) return;
-        ps_skinny<2>(ps_skinny_args(s.ctx, E, w.sa_out_w, w.sa_out_b, cur, s.x1, E, U, E, E, w.resweight), wg, G);
+        ps_skinny<2>(sa_out(w, x, d), wg, G);
         if (!ps_sync(bar)) return;
-        // cross attention over the cached K / V^T of the encoder window
-        ps_skinny<3>(ps_skinny_args(s.x1, E, w.ca_in_w, w.ca_in_b, nullptr, s.qkv, E, U, E, E, qscale), wg, G);
+        ps_skinny<3>(ca_q(w, x, d), wg, G);
         if (!ps_sync(bar)) return;
         {
-            AttnArgs c = {};
-            c.q = s.qkv; c.ldq = E; c.q_bs = (int64_t)U * E;
-            c.k = s.k_cache[l]; c.ldk = s.k_pitch ? s.k_pitch : E; c.k_bs = (int64_t)S * c.ldk;
-            c.vt = s.vt_cache[l]; c.ldvt = S4; c.vt_bs = (int64_t)E * S4;
-            c.vbias = w.ca_in_b + 2 * E;
-            c.kpm = s.kpm;
-            c.ctx = s.ctx; c.ldc = E; c.c_bs = (int64_t)U * E;
-            c.U = U; c.S = S; c.H = H;
-            c.probs = s.probs + (size_t)l * H * S; c.prob_row0 = U - 1;
+            const AttnArgs c = ca_attn(w, x, d, false);
             const int CB = split_cb(S), nblk = (S + 15) / 16, NCH = (nblk + CB - 1) / CB;
             const unsigned gx = (unsigned)((U + 15) / 16);
             for (unsigned vb = wg; vb < gx * (unsigned)H * (unsigned)NCH; vb += G) {
-                attn_split_body<HD, true>(c, CB, NCH, s.sk_part, s.tickets, Blk{vb % gx, (vb / gx) % (unsigned)H, vb / (gx * (unsigned)H), gx, (unsigned)H});
+                attn_split_body<HD, true>(c, CB, NCH, x.sk_part, x.tickets, Blk{vb % gx, (vb / gx) % (unsigned)H, vb / (gx * (unsigned)H), gx, (unsigned)H});
                 __syncthreads();
             }
         }
         if (!ps_sync(bar)) return;
-        ps_skinny<2>(ps_skinny_args(s.ctx, E, w.ca_out_w, w.ca_out_b, s.x1, s.x2, E, U, E, E, w.resweight_src), wg, G);
+        ps_skinny<2>(ca_out(w, x, d), wg, G);
         if (!ps_sync(bar)) return;
-        // feed-forward
-        ps_skinny<1>(ps_skinny_args(s.x2, E, w.lin1_w, w.lin1_b, nullptr, s.ff, FF, U, FF, E, 0.f), wg, G);
+        ps_skinny<1>(ff1(w, x, d), wg, G);
         if (!ps_sync(bar)) return;
-        {
-            SkinnyArgs f2 = ps_skinny_args(s.ff, FF, w.lin2_w, w.lin2_b, s.x2, s.h1, E, U, E, FF, w.resweight);
-            f2.ksplit = 4;
-            f2.sk_part = s.sk_part;
-            f2.sk_tickets = s.tickets + 64;
-            ps_skinny<2>(f2, wg, G);
-        }
+        ps_skinny<2>(ff2(w, x, d, false, true), wg, G);
         if (!ps_sync(bar)) return;
         cur = s.h1;
     }
     // ---- tied factorised LM head on the last position + pick + the new token's attention row (models.py:243-246, system.py:355-411)
     {
-        LmPickArgs q = {};
-        q.h = cur + (size_t)(U - 1) * E;
-        q.attn = s.probs;
-        q.layer_stride = (int64_t)H * S;
-        q.head_stride = (int64_t)S;
-        q.S = S;
-        q.partial = s.pick_part;
-        q.ticket_word = s.tickets + (TAL_GREEDY_TICKETS - 1);
-        q.out = s.out;
-        q.token_out = s.token_out;
-        q.host_seq = s.host_seq;
-        q.bias = nullptr;          // (a context with an LM row does not take the one-launch form: greedy_persist_ok)
+        // (no bias: a context with an LM row does not take the one-launch form: greedy_persist_ok)
+        const LmPickArgs q = lm_pick_args(cur + (size_t)(U - 1) * E, s.probs, (int64_t)H * S, (int64_t)S, S, s.pick_part, s.tickets, s.out,
+                                          s.token_out, s.host_seq, nullptr);
         const unsigned gx = (unsigned)((m.V + LMP_ROWS - 1) / LMP_ROWS);
         for (unsigned bx = wg; bx < gx; bx += G) {
             lm_pick_body(q, m.proj_t, E, K0, m.emb, m.V, m.n_layers, H, bx, gx);

@@ -15,8 +15,6 @@
 
 namespace tal {
 
-static inline int64_t pad4(int64_t n) { return (n + 3) & ~(int64_t)3; }
-
 __global__ __launch_bounds__(256) void embed_kernel(const int64_t* __restrict__ tokens, const float* __restrict__ emb,
                                                    const float* __restrict__ proj, const float* __restrict__ pe,
                                                    float* __restrict__ out, int U, int V, int E0, int D) {
@@ -409,13 +407,14 @@ struct LayerWs {
     size_t total_floats;
 };
 
+static size_t up64(size_t n) { return (n + 63) & ~(size_t)63; }
+
 static LayerWs carve(float* base, int B, int U, int S, int E, int H, int FF) {
     const int64_t L = U > S ? U : S;
     const int64_t L4 = pad4(L);
-    auto up = [](size_t n) { return (n + 63) & ~(size_t)63; };
     LayerWs w;
     size_t o = 0;
-    auto take = [&](size_t n) { float* p = base ? base + o : nullptr; o += up(n); return p; };
+    auto take = [&](size_t n) { float* p = base ? base + o : nullptr; o += up64(n); return p; };
     w.mha.q = take((size_t)B * U * 2 * E);   // q | k of the self-attention in one buffer
     w.mha.k = take((size_t)B * L * E);
     w.mha.vt = take((size_t)B * E * L4);
@@ -431,16 +430,6 @@ static LayerWs carve(float* base, int B, int U, int S, int E, int H, int FF) {
 }
 
 // ---- the same layer on the latency-oriented kernels (csrc/decode_small.hip): 8 launches instead of 13 ----------------
-static SkinnyArgs skinny(const float* A, int64_t lda, const float* W, const float* bias, const float* res, float* Y, int64_t ldy,
-                         int M, int N, int K, float alpha) {
-    SkinnyArgs g = {};
-    g.A = A; g.W = W; g.bias = bias; g.res = res; g.Y = Y;
-    g.M = M; g.N = N; g.K = K;
-    g.lda = lda; g.ldw = K; g.ldy = ldy; g.ldres = ldy;
-    g.alpha = alpha;
-    return g;
-}
-
 // Does a problem of `rows` rows run this layer in the folded form (6 launches)?  A function of the problem's OWN row count, so that a
 // session takes the same form -- the same bits -- alone and inside a merged step.  The fold trades two launches for a K axis twice
 // as long in two dense layers: it wins while the step is latency-bound (measured: -8 % per step at <= 32 prefix tokens, even at
@@ -457,8 +446,6 @@ static bool small_layer_applicable(int B, int U, int S, int E, int H, int FF, bo
            attn_small_applicable(U, S, E / H) && attn_small_applicable(U, U, E / H);
 }
 
-// probs_last != NULL: the cross-attention writes the per-head probabilities of the LAST prefix row only, [B][H][1][S]
-// (all the greedy loop reads); xattn_avg != NULL: the head-averaged weights of every row, [B][U][S].
 // scratch of the kernels that merge partial results in-launch (key-split attention, LM head + pick): the ticket words
 // must be zero before the first launch; every kernel leaves them zero
 struct DecodeScratch {
@@ -478,251 +465,111 @@ static size_t decode_scratch_floats(int U, int S, int E, int H) {
     return a > b ? a : b;
 }
 
-static int decoder_layer_small(const tal_decoder_layer_w* w, const float* tgt, int B, int U, int S, int E, int H, int FF,
-                               const float* tgt_mask, const uint8_t* mem_kpm, const float* ck, const float* cvt, float* out,
-                               float* xattn_avg, float* probs_last, const LayerWs& ws, hipStream_t s,
-                               const DecodeScratch* sk = nullptr, int64_t k_pitch = 0, bool allow_fold = true) {
-    const int M = B * U, hd = E / H;
-    const int64_t U4 = pad4(U), S4 = pad4(S);
-    const float qscale = 1.0f / sqrtf((float)hd);
-    // self attention: q | k | v^T in one launch (q scaled; v goes out transposed per batch item, bias folded after P.V)
-    float* qkv = ws.mha.q;                       // [M][3E]; the v columns of it are never written
-    SkinnyArgs g = skinny(tgt, E, w->sa_in_w, w->sa_in_b, nullptr, qkv, 3 * E, M, 3 * E, E, qscale);
-    g.scale_cols = E;
-    g.Yt = ws.mha.vt; g.vt_begin = 2 * E; g.U = U; g.ldt = U4; g.vt_bs = (int64_t)E * U4;
-    // (the v bias is part of the packed bias and so goes into V^T here; P . (V + b) = P . V + b because rows of P sum to 1)
-    int rc = launch_skinny_gemm(g, 3, s);
-    if (rc) return rc;
-    AttnArgs a = {};
-    a.q = qkv; a.ldq = 3 * E; a.q_bs = (int64_t)U * 3 * E;
-    a.k = qkv + E; a.ldk = 3 * E; a.k_bs = (int64_t)U * 3 * E;
-    a.vt = ws.mha.vt; a.ldvt = U4; a.vt_bs = (int64_t)E * U4;
-    a.vbias = nullptr;                            // already inside V^T
-    a.mask = tgt_mask; a.kpm = nullptr;
-    a.ctx = ws.mha.ctx; a.ldc = E; a.c_bs = (int64_t)U * E;
-    a.U = U; a.S = U; a.H = H;
-    rc = launch_attn_small(a, B, hd, s);
-    if (rc) return rc;
-    // Folded form (tal_decoder_layer_w.fold_*): the self-attention's out-projection + ReZero and the cross-attention's q projection are
-    // ONE dense layer over [ctx | tgt] (x1 | q_c side by side in y3), and so are the cross-attention's out-projection + ReZero and
-    // FFN-1 over [ctx2 | x1] (x2 | ff in y5): 6 dependent launches per layer instead of 8.
-    const bool fold = allow_fold && layer_folded(w, E, M);
-    const float* qc;
-    int64_t ldq;
-    if (fold) {
-        SkinnyArgs g3 = skinny(ws.mha.ctx, E, w->fold_sa_w, w->fold_sa_b, nullptr, ws.y3, 2 * E, M, 2 * E, 2 * E, 0.f);
-        g3.A2 = tgt; g3.lda2 = E; g3.K1 = E; g3.k1_cols = E;
-        rc = launch_skinny_gemm(g3, 0, s);
-        if (rc) return rc;
-        qc = ws.y3 + E;
-        ldq = 2 * E;
-    } else {
-        rc = launch_skinny_gemm(skinny(ws.mha.ctx, E, w->sa_out_w, w->sa_out_b, tgt, ws.x1, E, M, E, E, w->resweight), 2, s);
-        if (rc) return rc;
-        // cross attention over the cached K / V^T of the encoder window
-        rc = launch_skinny_gemm(skinny(ws.x1, E, w->ca_in_w, w->ca_in_b, nullptr, ws.mha.q, E, M, E, E, qscale), 3, s);
-        if (rc) return rc;
-        qc = ws.mha.q;
-        ldq = E;
-    }
-    AttnArgs c = {};
-    c.q = qc; c.ldq = ldq; c.q_bs = (int64_t)U * ldq;
-    c.k = ck; c.ldk = k_pitch ? k_pitch : E; c.k_bs = (int64_t)S * c.ldk;      // (k_pitch: the window is a view of an episode-wide K | V table)
-    c.vt = cvt; c.ldvt = S4; c.vt_bs = (int64_t)E * S4;
-    c.vbias = w->ca_in_b + 2 * E;
-    c.mask = nullptr; c.kpm = mem_kpm;
-    c.ctx = ws.mha.ctx; c.ldc = E; c.c_bs = (int64_t)U * E;
-    c.U = U; c.S = S; c.H = H;
-    if (xattn_avg) { c.probs = ws.mha.scores; c.prob_row0 = 0; }
-    else if (probs_last) { c.probs = probs_last; c.prob_row0 = U - 1; }
-    // long key axis + scratch available: cut the keys over workgroups (8x the CUs pulling K / V^T)
-    if (sk && S > 64 && attn_split_tickets(B, U, H) <= 64)
-        rc = launch_attn_split(c, B, hd, sk->part, sk->tickets, s);
-    else
-        rc = launch_attn_small(c, B, hd, s);
-    if (rc) return rc;
-    if (xattn_avg) {
-        rc = launch_head_average(ws.mha.scores, xattn_avg, B, H, U, S, s);
-        if (rc) return rc;
-    }
-    SkinnyArgs f2;
-    if (fold) {
-        SkinnyArgs g5 = skinny(ws.mha.ctx, E, w->fold_ca_w, w->fold_ca_b, nullptr, ws.y5, E + FF, M, E + FF, 2 * E, 0.f);
-        g5.A2 = ws.y3; g5.lda2 = 2 * E; g5.K1 = E; g5.k1_cols = E;          // x1 = the first E columns of y3
-        g5.relu_begin = E;                                   // x2 plain, ff through the relu
-        rc = launch_skinny_gemm(g5, 1, s);
-        if (rc) return rc;
-        f2 = skinny(ws.y5 + E, E + FF, w->lin2_w, w->lin2_b, ws.y5, out, E, M, E, FF, w->resweight);
-        f2.ldw = FF;
-        f2.ldres = E + FF;
-    } else {
-        rc = launch_skinny_gemm(skinny(ws.mha.ctx, E, w->ca_out_w, w->ca_out_b, ws.x1, ws.x2, E, M, E, E, w->resweight_src), 2, s);
-        if (rc) return rc;
-        // feed-forward
-        rc = launch_skinny_gemm(skinny(ws.x2, E, w->lin1_w, w->lin1_b, nullptr, ws.ff, FF, M, FF, E, 0.f), 1, s);
-        if (rc) return rc;
-        f2 = skinny(ws.ff, FF, w->lin2_w, w->lin2_b, ws.x2, out, E, M, E, FF, w->resweight);
-    }
-    if (sk && FF >= 2048 && FF % 256 == 0 && (E / 16) * ((M + 31) / 32) <= TAL_GREEDY_TICKETS - 64) {
-        // K = FF is deep: four workgroups per tile, each pulling a quarter of the operands (tickets 64 .. 254)
-        f2.ksplit = 4;
-        f2.sk_part = sk->part;
-        f2.sk_tickets = sk->tickets + 64;
-    }
-    return launch_skinny_gemm(f2, 2, s);
+// ---- which kernel form a problem takes: each rule once (the launch chain, the merged step and the one-launch step must agree) ----
+// long key axis: the keys of the cross-attention cut over workgroups (8x the CUs pulling K / V^T) while its (row block, head) groups
+// fit 64 tickets
+static bool attn_split_form(int B, int U, int S, int H) { return S > 64 && attn_split_tickets(B, U, H) <= 64; }
+// K = FF is deep: FFN-2 cut along K while its tiles fit the tickets 64 .. 254
+static bool ffn2_ksplit_form(int E, int FF, int rows) {
+    return FF >= 2048 && FF % 256 == 0 && (E / 16) * ((rows + 31) / 32) <= TAL_GREEDY_TICKETS - 64;
+}
+// LM head + pick as one launch (lm_pick_kernel): the only form that writes a result, and its sequence word, to pinned host memory
+static bool merged_pick_ok(const tal_greedy_ctx* c) {
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    return c->tickets && c->E % 16 == 0 && (c->E0 > 0 ? c->E0 : c->E) % 8 == 0 && al16(c->emb) && (!c->proj_t || al16(c->proj_t));
 }
 
-// The same layer for the decode steps of G sessions at once (batch 1 each, own prefix length / window / buffers): every launch of
-// decoder_layer_small becomes ONE launch over all sessions (the multi forms of csrc/decode_small.hip), so a step of G sessions
-// costs the 8 dependent launches of one.  A session's rows go through the same kernel bodies with the same arguments as in
-// decoder_layer_small: bit-identical.  All sessions must take the SAME kernel forms there (key-split cross-attention, FFN-2 cut
-// along K): greedy_group_ok checks it.
-struct SessionLayerIo {
-    const float* tgt;        // [U, E]
-    int U, S;
-    const uint8_t* mem_kpm;
-    const float* ck;
-    int64_t k_pitch;         // floats between the window's K rows (E, or the pitch of the episode-wide K | V table)
-    const float* cvt;
-    float* out;
-    float* probs_last;       // [H][S]
-    LayerWs ws;
-    DecodeScratch sk;
-    bool no_fold;            // the session's tal_greedy_ctx.no_fold
-};
-static int decoder_layer_small_multi_form(const tal_decoder_layer_w* w, const SessionLayerIo* io, int G, int E, int H, int FF, bool fold, hipStream_t s);
-// (sessions on either side of the fold's row limit go through the layer as two groups of launches: each in the form its solo step takes)
-static int decoder_layer_small_multi(const tal_decoder_layer_w* w, const SessionLayerIo* io, int G, int E, int H, int FF, hipStream_t s) {
-    SessionLayerIo part[2][TAL_GROUP_MAX];
-    int n[2] = {0, 0};
-    for (int i = 0; i < G; ++i) {
-        const int f = (!io[i].no_fold && layer_folded(w, E, io[i].U)) ? 1 : 0;
-        part[f][n[f]++] = io[i];
-    }
-    for (int f = 1; f >= 0; --f)
-        if (n[f] > 0) {
-            const int rc = decoder_layer_small_multi_form(w, part[f], n[f], E, H, FF, f == 1, s);
-            if (rc) return rc;
-        }
-    return TAL_OK;
+static LayerDims layer_dims(int E, int H, int FF) { return LayerDims{E, H, FF, 1.0f / sqrtf((float)(E / H))}; }
+// a problem's view of a layer on the workspace `ws`; the caller adds the masks, the cached K / V^T, the probabilities and the scratch
+static LayerIo layer_io(const LayerWs& ws, const float* tgt, float* out, int B, int U, int S) {
+    LayerIo x = {};
+    x.tgt = tgt; x.out = out; x.B = B; x.U = U; x.S = S;
+    x.qkv = ws.mha.q; x.vt = ws.mha.vt; x.ctx = ws.mha.ctx; x.x1 = ws.x1; x.x2 = ws.x2; x.ff = ws.ff; x.y3 = ws.y3; x.y5 = ws.y5;
+    return x;
 }
-static int decoder_layer_small_multi_form(const tal_decoder_layer_w* w, const SessionLayerIo* io, int G, int E, int H, int FF, bool fold, hipStream_t s) {
-    const int hd = E / H;
-    const float qscale = 1.0f / sqrtf((float)hd);
+
+// The layer for G problems: build each phase's arguments (csrc/decode_bodies.h), launch.  multi: every phase is ONE launch over all
+// problems (the multi forms of csrc/decode_small.hip; batch 1 each, own prefix length / window / buffers), so a step of G sessions costs
+// the dependent launches of one; otherwise G == 1 on the single-problem kernels.  A problem's rows go through the same kernel bodies
+// with the same arguments either way: bit-identical.  All problems of a call take the SAME forms: fold, split (key-split
+// cross-attention), ksplit (FFN-2 cut along K).  xattn_avg (single problem only): the head-averaged cross-attention weights of every
+// row, [B][U][S], from the per-head probabilities in io[0].probs.
+static int decoder_layer_walk(const tal_decoder_layer_w& w, const LayerIo* io, int G, bool multi, const LayerDims& d, bool fold, bool split,
+                              bool ksplit, float* xattn_avg, hipStream_t s) {
+    const int hd = d.E / d.H;
     SkinnyArgs g[TAL_GROUP_MAX];
     AttnArgs a[TAL_GROUP_MAX];
     float* scr[TAL_GROUP_MAX];
     unsigned* tik[TAL_GROUP_MAX];
-    for (int i = 0; i < G; ++i) {
-        const SessionLayerIo& x = io[i];
-        const int64_t U4 = pad4(x.U);
-        g[i] = skinny(x.tgt, E, w->sa_in_w, w->sa_in_b, nullptr, x.ws.mha.q, 3 * E, x.U, 3 * E, E, qscale);
-        g[i].scale_cols = E;
-        g[i].Yt = x.ws.mha.vt; g[i].vt_begin = 2 * E; g[i].U = x.U; g[i].ldt = U4; g[i].vt_bs = (int64_t)E * U4;
-    }
-    int rc = launch_skinny_gemm_multi(g, G, 3, s);
+    auto dense = [&](int mode, auto build) {
+        for (int i = 0; i < G; ++i) g[i] = build(io[i]);
+        return multi ? launch_skinny_gemm_multi(g, G, mode, s) : launch_skinny_gemm(g[0], mode, s);
+    };
+    auto attn = [&](bool cut, auto build) {
+        for (int i = 0; i < G; ++i) { a[i] = build(io[i]); scr[i] = io[i].sk_part; tik[i] = io[i].tickets; }
+        if (cut) return multi ? launch_attn_split_multi(a, scr, tik, G, hd, s) : launch_attn_split(a[0], io[0].B, hd, scr[0], tik[0], s);
+        return multi ? launch_attn_small_multi(a, G, hd, s) : launch_attn_small(a[0], io[0].B, hd, s);
+    };
+    int rc = dense(3, [&](const LayerIo& x) { return sa_qkv(w, x, d); });
     if (rc) return rc;
-    for (int i = 0; i < G; ++i) {
-        const SessionLayerIo& x = io[i];
-        const int64_t U4 = pad4(x.U);
-        float* qkv = x.ws.mha.q;
-        a[i] = AttnArgs{};
-        a[i].q = qkv; a[i].ldq = 3 * E; a[i].q_bs = (int64_t)x.U * 3 * E;
-        a[i].k = qkv + E; a[i].ldk = 3 * E; a[i].k_bs = (int64_t)x.U * 3 * E;
-        a[i].vt = x.ws.mha.vt; a[i].ldvt = U4; a[i].vt_bs = (int64_t)E * U4;
-        a[i].ctx = x.ws.mha.ctx; a[i].ldc = E; a[i].c_bs = (int64_t)x.U * E;
-        a[i].U = x.U; a[i].S = x.U; a[i].H = H;
-    }
-    rc = launch_attn_small_multi(a, G, hd, s);
-    if (rc) return rc;
-    // (fold: the same arguments per session as decoder_layer_small builds: bit-identical)
-    if (fold) {
-        for (int i = 0; i < G; ++i) {
-            g[i] = skinny(io[i].ws.mha.ctx, E, w->fold_sa_w, w->fold_sa_b, nullptr, io[i].ws.y3, 2 * E, io[i].U, 2 * E, 2 * E, 0.f);
-            g[i].A2 = io[i].tgt; g[i].lda2 = E; g[i].K1 = E; g[i].k1_cols = E;
-        }
-        rc = launch_skinny_gemm_multi(g, G, 0, s);
-        if (rc) return rc;
-    } else {
-        for (int i = 0; i < G; ++i) g[i] = skinny(io[i].ws.mha.ctx, E, w->sa_out_w, w->sa_out_b, io[i].tgt, io[i].ws.x1, E, io[i].U, E, E, w->resweight);
-        rc = launch_skinny_gemm_multi(g, G, 2, s);
-        if (rc) return rc;
-        for (int i = 0; i < G; ++i) g[i] = skinny(io[i].ws.x1, E, w->ca_in_w, w->ca_in_b, nullptr, io[i].ws.mha.q, E, io[i].U, E, E, qscale);
-        rc = launch_skinny_gemm_multi(g, G, 3, s);
-        if (rc) return rc;
-    }
-    const int64_t ldq = fold ? 2 * E : E;
-    for (int i = 0; i < G; ++i) {
-        const SessionLayerIo& x = io[i];
-        const int64_t S4 = pad4(x.S);
-        a[i] = AttnArgs{};
-        a[i].q = fold ? x.ws.y3 + E : x.ws.mha.q; a[i].ldq = ldq; a[i].q_bs = (int64_t)x.U * ldq;
-        a[i].k = x.ck; a[i].ldk = x.k_pitch; a[i].k_bs = (int64_t)x.S * x.k_pitch;
-        a[i].vt = x.cvt; a[i].ldvt = S4; a[i].vt_bs = (int64_t)E * S4;
-        a[i].vbias = w->ca_in_b + 2 * E;
-        a[i].kpm = x.mem_kpm;
-        a[i].ctx = x.ws.mha.ctx; a[i].ldc = E; a[i].c_bs = (int64_t)x.U * E;
-        a[i].U = x.U; a[i].S = x.S; a[i].H = H;
-        a[i].probs = x.probs_last; a[i].prob_row0 = x.U - 1;
-        scr[i] = x.sk.part;
-        tik[i] = x.sk.tickets;
-    }
-    rc = launch_attn_split_multi(a, scr, tik, G, hd, s);
+    rc = attn(false, [&](const LayerIo& x) { return sa_attn(x, d); });
     if (rc) return rc;
     if (fold) {
-        for (int i = 0; i < G; ++i) {
-            g[i] = skinny(io[i].ws.mha.ctx, E, w->fold_ca_w, w->fold_ca_b, nullptr, io[i].ws.y5, E + FF, io[i].U, E + FF, 2 * E, 0.f);
-            g[i].A2 = io[i].ws.y3; g[i].lda2 = 2 * E; g[i].K1 = E; g[i].k1_cols = E;
-            g[i].relu_begin = E;
-        }
-        rc = launch_skinny_gemm_multi(g, G, 1, s);
-        if (rc) return rc;
+        rc = dense(0, [&](const LayerIo& x) { return fold_sa(w, x, d); });
     } else {
-        for (int i = 0; i < G; ++i) g[i] = skinny(io[i].ws.mha.ctx, E, w->ca_out_w, w->ca_out_b, io[i].ws.x1, io[i].ws.x2, E, io[i].U, E, E, w->resweight_src);
-        rc = launch_skinny_gemm_multi(g, G, 2, s);
+        rc = dense(2, [&](const LayerIo& x) { return sa_out(w, x, d); });
         if (rc) return rc;
-        for (int i = 0; i < G; ++i) g[i] = skinny(io[i].ws.x2, E, w->lin1_w, w->lin1_b, nullptr, io[i].ws.ff, FF, io[i].U, FF, E, 0.f);
-        rc = launch_skinny_gemm_multi(g, G, 1, s);
+        rc = dense(3, [&](const LayerIo& x) { return ca_q(w, x, d); });
+    }
+    if (rc) return rc;
+    rc = attn(split, [&](const LayerIo& x) { return ca_attn(w, x, d, fold); });
+    if (rc) return rc;
+    if (xattn_avg) {
+        rc = launch_head_average(io[0].probs, xattn_avg, io[0].B, d.H, io[0].U, io[0].S, s);
         if (rc) return rc;
     }
-    for (int i = 0; i < G; ++i) {
-        if (fold) {
-            g[i] = skinny(io[i].ws.y5 + E, E + FF, w->lin2_w, w->lin2_b, io[i].ws.y5, io[i].out, E, io[i].U, E, FF, w->resweight);
-            g[i].ldres = E + FF;
-        } else {
-            g[i] = skinny(io[i].ws.ff, FF, w->lin2_w, w->lin2_b, io[i].ws.x2, io[i].out, E, io[i].U, E, FF, w->resweight);
-        }
-        g[i].ksplit = 4;
-        g[i].sk_part = io[i].sk.part;
-        g[i].sk_tickets = io[i].sk.tickets + 64;
+    if (fold) {
+        rc = dense(1, [&](const LayerIo& x) { return fold_ca(w, x, d); });
+    } else {
+        rc = dense(2, [&](const LayerIo& x) { return ca_out(w, x, d); });
+        if (rc) return rc;
+        rc = dense(1, [&](const LayerIo& x) { return ff1(w, x, d); });
     }
-    return launch_skinny_gemm_multi(g, G, 2, s);
+    if (rc) return rc;
+    return dense(2, [&](const LayerIo& x) { return ff2(w, x, d, fold, ksplit); });
+}
+
+// ONE problem on the single-problem kernels.  Only this form takes batch > 1, a target mask, xattn_avg (x.probs: every row's per-head
+// probabilities, prob_row0 = 0) and a caller without scratch (x.tickets == NULL: no key-split attention, no split K).
+static int decoder_layer_small(const tal_decoder_layer_w* w, const LayerIo& x, int E, int H, int FF, bool allow_fold, float* xattn_avg,
+                               hipStream_t s) {
+    const int M = x.B * x.U;
+    return decoder_layer_walk(*w, &x, 1, false, layer_dims(E, H, FF), allow_fold && layer_folded(w, E, M),
+                              x.tickets && attn_split_form(x.B, x.U, x.S, H), x.tickets && ffn2_ksplit_form(E, FF, M), xattn_avg, s);
 }
 
 // may a step of (U, S) run as ONE launch (csrc/decode_persist.hip)?  The shapes the merged launches take (so that every phase is the
 // kernel form the launch chain uses for this step), dense layers no deeper than 512 per K slice (four waves per workgroup), and the
 // FFN's split-K tickets ending below the words the one-launch step keeps its counters in.
 static bool greedy_persist_ok(const tal_greedy_ctx* c, int U, int S) {
-    const int E = c->E, H = c->H, FF = c->FF, K0 = c->E0 > 0 ? c->E0 : c->E, hd = E / H;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const int E = c->E, H = c->H, FF = c->FF, hd = E / H;
     // (the one-launch form walks the UNFOLDED layer's phases: it is a measurement switch of round 5, valid beside option decode_no_fold)
-    return c->tickets && !c->pick_bias && (c->no_fold || !layer_folded(&c->layers[0], c->E, U)) && c->n_layers <= TAL_PS_MAX_LAYERS && (hd == 128 || hd == 64) && E <= 512 && FF / 4 <= 512 && E % 64 == 0 &&
-           small_layer_applicable(1, U, S, E, H, FF, true) && S > 64 && attn_split_tickets(1, U, H) <= 64 && FF >= 2048 && FF % 256 == 0 &&
-           64 + (E / 16) * ((U + 31) / 32) <= PS_BAR && E % 16 == 0 && K0 % 8 == 0 && al16(c->emb) && (!c->proj_t || al16(c->proj_t));
+    return merged_pick_ok(c) && !c->pick_bias && (c->no_fold || !layer_folded(&c->layers[0], c->E, U)) && c->n_layers <= TAL_PS_MAX_LAYERS &&
+           (hd == 128 || hd == 64) && E <= 512 && FF / 4 <= 512 && E % 64 == 0 && small_layer_applicable(1, U, S, E, H, FF, true) &&
+           attn_split_form(1, U, S, H) && ffn2_ksplit_form(E, FF, U) && 64 + (E / 16) * ((U + 31) / 32) <= PS_BAR;
 }
 static void ps_fill_model(const tal_greedy_ctx* c, PsModel& m) {
     m = PsModel{};
     for (int l = 0; l < c->n_layers; ++l) m.layer[l] = c->layers[l];
     m.n_layers = c->n_layers; m.E = c->E; m.H = c->H; m.FF = c->FF; m.V = c->V;
     m.K0 = c->E0 > 0 ? c->E0 : c->E;
-    m.qscale = 1.0f / sqrtf((float)(c->E / c->H));
+    m.qscale = layer_dims(c->E, c->H, c->FF).qscale;
     m.emb = c->emb; m.proj = c->E0 > 0 ? c->proj : nullptr; m.proj_t = c->E0 > 0 ? c->proj_t : nullptr; m.pe = c->pe;
 }
 
-// does a session's step take, in decoder_layer_small, exactly the kernel forms decoder_layer_small_multi launches?
+// does a session's step take, in decoder_layer_small, exactly the kernel forms the merged step launches?
 static bool greedy_group_ok(int U, int S, int E, int H, int FF) {
-    return small_layer_applicable(1, U, S, E, H, FF, true) && S > 64 && attn_split_tickets(1, U, H) <= 64 &&
-           FF >= 2048 && FF % 256 == 0 && (E / 16) * ((U + 31) / 32) <= TAL_GREEDY_TICKETS - 64;
+    return small_layer_applicable(1, U, S, E, H, FF, true) && attn_split_form(1, U, S, H) && ffn2_ksplit_form(E, FF, U);
 }
 
 }  // namespace tal
@@ -801,8 +648,12 @@ static int decoder_layer_pitched(const tal_decoder_layer_w* w, const float* tgt,
     }
     hipStream_t s = (hipStream_t)stream;
     LayerWs ws = carve(reinterpret_cast<float*>(workspace), B, U, S, E, H, FF);
-    if (small_layer_applicable(B, U, S, E, H, FF, k_cache && vt_cache))
-        return decoder_layer_small(w, tgt, B, U, S, E, H, FF, tgt_mask, mem_kpm, k_cache, vt_cache, out, xattn_avg, nullptr, ws, s, nullptr, k_pitch);
+    if (small_layer_applicable(B, U, S, E, H, FF, k_cache && vt_cache)) {
+        LayerIo x = layer_io(ws, tgt, out, B, U, S);
+        x.tgt_mask = tgt_mask; x.kpm = mem_kpm; x.ck = k_cache; x.cvt = vt_cache; x.k_pitch = k_pitch;
+        if (xattn_avg) x.probs = ws.mha.scores;
+        return decoder_layer_small(w, x, E, H, FF, true, xattn_avg, s);
+    }
     // self attention over the prefix: q|k in one launch, V^T, scores/softmax/PV, out-proj + ReZero
     int rc = project_q_or_qk(w->sa_in_w, w->sa_in_b, tgt, (int64_t)B * U, E, H, 2, ws.mha.q, s);
     if (rc) return rc;
@@ -914,22 +765,49 @@ extern "C" int tal_log_softmax_rows(const float* x, int64_t M, int N, float* out
 // position -> token = argmax(log_softmax) + the new token's layer- and head-averaged cross-attention row -> append the
 // token to the device-resident prefix -> (sync != 0) copy {token, row} to pinned host memory and wait.
 // ---------------------------------------------------------------------------------------------------------------
-static size_t up64(size_t n) { return (n + 63) & ~(size_t)63; }
+// A session's step workspace: the layer's buffers, then the step's own.  base == NULL: sizes only.
+struct StepWs {
+    LayerWs layer;
+    float *h0, *h1;          // embedded prefix, stack output [U][E]
+    float* avg;              // attention rows of the batched-GEMM layer, head-averaged [L][U][S]
+    float* probs;            // attention rows of the latency-oriented layer, per-head last rows [L][H][S]
+    float *lm_t, *logits;    // LM head intermediate, logits (the unmerged LM head + pick)
+    DecodeScratch sk;        // key-split attention records / split-K partial tiles
+    float* pick_part;        // pick partials
+    size_t total_floats;
+};
+static StepWs carve_step(float* base, unsigned* tickets, int U, int S, int E, int H, int FF, int V, int E0, int L) {
+    StepWs w;
+    w.layer = carve(base, 1, U, S, E, H, FF);
+    size_t o = w.layer.total_floats;
+    auto take = [&](size_t n) { float* p = base ? base + o : nullptr; o += up64(n); return p; };
+    w.h0 = take((size_t)U * E);
+    w.h1 = take((size_t)U * E);
+    w.avg = take((size_t)L * U * S);
+    w.probs = take((size_t)L * H * S);
+    w.lm_t = take((size_t)(E0 > 0 ? E0 : E));
+    w.logits = take((size_t)V);
+    w.sk = {take(decode_scratch_floats(U, S, E, H)), tickets};
+    w.pick_part = take((size_t)2 * cdiv(V, LMP_ROWS));
+    w.total_floats = o;
+    return w;
+}
 
 extern "C" size_t tal_greedy_step_workspace_bytes(int U_max, int S, int E, int H, int FF, int V, int E0, int n_layers) {
     if (U_max <= 0 || S <= 0 || E <= 0 || H <= 0 || FF <= 0 || V <= 0 || n_layers <= 0) return 0;
-    size_t f = carve(nullptr, 1, U_max, S, E, H, FF).total_floats;
-    f += 2 * up64((size_t)U_max * E);                        // embedded prefix, stack output
-    f += up64((size_t)n_layers * (size_t)U_max * S);         // attention rows: per-head last rows [L][H][S] or averaged [L][U][S]
-    f += up64((size_t)n_layers * H * S);
-    f += up64((size_t)(E0 > 0 ? E0 : E)) + up64((size_t)V);   // LM head intermediate, logits
-    f += up64(decode_scratch_floats(U_max, S, E, H));         // key-split attention records / split-K partial tiles
-    f += up64((size_t)2 * cdiv(V, LMP_ROWS));                 // pick partials
-    return f * sizeof(float);
+    return carve_step(nullptr, nullptr, U_max, S, E, H, FF, V, E0, n_layers).total_floats * sizeof(float);
 }
 
-// 1: the result of the context's latest host-direct step (sync 2 / 3) is in picked_host; 0: not yet, after waiting up to
-// wait_ms milliseconds (0: one look); < 0: bad argument.  Host-only: reads the sequence word the pick kernel writes last.
+// layer l of a greedy session's step on the latency-oriented kernels: the window's cached K / V^T (k_pitch: the window is a view of an
+// episode-wide K | V table), the last prefix row's per-head probabilities [H][S] (all the greedy loop reads), the context's scratch
+static LayerIo greedy_layer_io(const tal_greedy_ctx* c, const StepWs& w, int l, int U) {
+    LayerIo x = layer_io(w.layer, l == 0 ? w.h0 : w.h1, w.h1, 1, U, c->S);
+    x.kpm = c->mem_kpm; x.ck = c->k_cache[l]; x.cvt = c->vt_cache[l]; x.k_pitch = c->k_pitch;
+    x.probs = w.probs + (size_t)l * c->H * c->S; x.prob_row0 = U - 1;
+    if (c->tickets) { x.sk_part = w.sk.part; x.tickets = w.sk.tickets; }
+    return x;
+}
+
 // A context whose last step failed part-way (needs_reset) starts its next step from a zeroed ticket block, behind everything the
 // failed step may still have in flight.
 static int greedy_reset_if_needed(tal_greedy_ctx* c, hipStream_t s) {
@@ -950,7 +828,38 @@ static int greedy_failed_marker(tal_greedy_ctx* c, const char* who) {
               "died); no token was produced, the context's ticket block is reset before its next step", who);
     return TAL_EHIP;
 }
+// Host-direct results: the pick writes {token, row, sequence word} straight into the pinned host buffer (1 + S + 1 words) through its
+// device alias, set up on a context's first such step (a recycled buffer may hold an old sequence value: the word is cleared).
+static int greedy_host_alias(tal_greedy_ctx* c, const char* who, int session = -1) {
+    if (c->picked_host_dev) return TAL_OK;
+    void* alias = nullptr;
+    if (hipHostGetDevicePointer(&alias, c->picked_host, 0) != hipSuccess || !alias) {
+        char sess[24] = "";
+        if (session >= 0) snprintf(sess, sizeof(sess), " session %d:", session);
+        set_error("%s:%s picked_host is not mapped pinned host memory (%s)", who, sess, hipGetErrorString(hipGetLastError()));
+        return TAL_EINVAL;
+    }
+    c->picked_host_dev = reinterpret_cast<float*>(alias);
+    reinterpret_cast<volatile unsigned*>(c->picked_host)[1 + c->S] = 0u;
+    return TAL_OK;
+}
+// the sequence value of the context's next host-direct step (one context per stream); never 0, the value of a buffer nobody has written yet
+static unsigned greedy_next_seq(tal_greedy_ctx* c) {
+    if (++c->seq == 0) ++c->seq;
+    return c->seq;
+}
+// the copy form of a synchronous step: {token, row} from picked_dev to the pinned host buffer, and wait
+static int greedy_copy_result(tal_greedy_ctx* c, hipStream_t s) {
+    if (hipMemcpyAsync(c->picked_host, c->picked_dev, (size_t)(1 + c->S) * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        set_error("tal_greedy_step_fwd: device-to-host copy failed: %s", hipGetErrorString(hipGetLastError()));
+        return TAL_EHIP;
+    }
+    return TAL_OK;
+}
 
+// 1: the result of the context's latest host-direct step (sync 2 / 3) is in picked_host; 0: not yet, after waiting up to
+// wait_ms milliseconds (0: one look); < 0: bad argument.  Host-only: reads the sequence word the pick kernel writes last.
 extern "C" int tal_greedy_step_poll(tal_greedy_ctx* c, int wait_ms) {
     TAL_CHECK_ARG(c && c->picked_host && c->S > 0 && wait_ms >= 0, "tal_greedy_step_poll: bad argument");
     volatile unsigned* flag = reinterpret_cast<volatile unsigned*>(c->picked_host + 1 + c->S);
@@ -976,8 +885,7 @@ extern "C" int tal_greedy_step_fwd(tal_greedy_ctx* c, int64_t history_start, int
                   (long long)history_start, (long long)n_gen, c->max_len);
     TAL_CHECK_ARG(sync >= 0 && sync <= 3, "tal_greedy_step_fwd: sync=%d", sync);
     TAL_CHECK_ARG(!sync || c->picked_host, "tal_greedy_step_fwd: sync needs the pinned host buffer");
-    TAL_CHECK_ARG(sync != 3 || (c->tickets && c->E % 16 == 0 && (c->E0 > 0 ? c->E0 : c->E) % 8 == 0 && (reinterpret_cast<uintptr_t>(c->emb) & 15) == 0 &&
-                                (!c->proj_t || (reinterpret_cast<uintptr_t>(c->proj_t) & 15) == 0)),
+    TAL_CHECK_ARG(sync != 3 || merged_pick_ok(c),
                   "tal_greedy_step_fwd: sync 3 (result written to pinned memory, polled by the caller) needs the merged LM-head + pick kernel "
                   "(tickets, E %% 16 == 0, embedding width %% 8 == 0, 16-byte aligned emb / proj_t): nothing else writes the sequence word");
     const int U = (int)U64;
@@ -988,31 +896,15 @@ extern "C" int tal_greedy_step_fwd(tal_greedy_ctx* c, int64_t history_start, int
     hipStream_t s = (hipStream_t)stream;
     if (int rr = greedy_reset_if_needed(c, s)) return rr;
     float* base = reinterpret_cast<float*>(c->workspace);
-    LayerWs ws = carve(base, 1, U, S, E, H, FF);
-    float* p = base + ws.total_floats;
-    float* h0 = p; p += up64((size_t)U * E);
-    float* h1 = p; p += up64((size_t)U * E);
-    float* avg = p; p += up64((size_t)L * U * S);
-    float* probs = p; p += up64((size_t)L * H * S);
-    float* lm_t = p; p += up64((size_t)(E0 > 0 ? E0 : E));
-    float* logits = p; p += up64((size_t)V);
-    DecodeScratch sk = {p, c->tickets};
-    p += up64(decode_scratch_floats(U, S, E, H));
-    float* pick_part = p;
+    const StepWs w = carve_step(base, c->tickets, U, S, E, H, FF, V, E0, L);
+    // sync == 2 / 3: host-direct; sync 2 polls the sequence word here, sync 3 leaves the polling to the caller (tal_greedy_step_poll:
+    // several sessions in flight on several streams)
+    const bool host_direct = sync >= 2 && c->tickets;
     if (opt(OPT_DECODE_PERSIST) != 0 && greedy_persist_ok(c, U, S)) {
         // ---- the whole step as ONE launch (csrc/decode_persist.hip): the same kernel bodies on the same arguments behind phase barriers
         for (int l = 0; l < L; ++l) TAL_CHECK_ARG(c->k_cache[l] && c->vt_cache[l], "tal_greedy_step_fwd: layer %d has no cached K / V^T", l);
-        const bool host_direct = sync >= 2;
-        if (host_direct && !c->picked_host_dev) {
-            void* alias = nullptr;
-            if (hipHostGetDevicePointer(&alias, c->picked_host, 0) != hipSuccess || !alias) {
-                set_error("tal_greedy_step_fwd: picked_host is not mapped pinned host memory (%s)", hipGetErrorString(hipGetLastError()));
-                return TAL_EINVAL;
-            }
-            c->picked_host_dev = reinterpret_cast<float*>(alias);
-            reinterpret_cast<volatile unsigned*>(c->picked_host)[1 + S] = 0u;
-        }
-        if (host_direct && ++c->seq == 0) ++c->seq;
+        if (host_direct)
+            if (int rc = greedy_host_alias(c, "tal_greedy_step_fwd")) return rc;
         PsArgs a;
         ps_fill_model(c, a.m);
         a.n = 1;
@@ -1021,13 +913,14 @@ extern "C" int tal_greedy_step_fwd(tal_greedy_ctx* c, int64_t history_start, int
         q = PsSession{};
         q.tokens = c->tokens + history_start; q.token_out = c->tokens + n_gen;
         q.U = U; q.S = S;
-        q.h0 = h0; q.h1 = h1; q.qkv = ws.mha.q; q.vt = ws.mha.vt; q.ctx = ws.mha.ctx; q.x1 = ws.x1; q.x2 = ws.x2; q.ff = ws.ff;
-        q.probs = probs; q.sk_part = sk.part; q.pick_part = pick_part;
+        q.h0 = w.h0; q.h1 = w.h1; q.qkv = w.layer.mha.q; q.vt = w.layer.mha.vt; q.ctx = w.layer.mha.ctx;
+        q.x1 = w.layer.x1; q.x2 = w.layer.x2; q.ff = w.layer.ff;
+        q.probs = w.probs; q.sk_part = w.sk.part; q.pick_part = w.pick_part;
         q.out = host_direct ? c->picked_host_dev : c->picked_dev;
         q.tickets = c->tickets;
         for (int l = 0; l < L; ++l) { q.k_cache[l] = c->k_cache[l]; q.vt_cache[l] = c->vt_cache[l]; }
         q.kpm = c->mem_kpm; q.k_pitch = c->k_pitch;
-        q.host_seq = host_direct ? c->seq : 0u;
+        q.host_seq = host_direct ? greedy_next_seq(c) : 0u;
         int rc = launch_greedy_persist(a, s);
         if (rc) return rc;
         // sync 0: the caller reads picked_dev itself -- a token of -1 there is the failure marker (include/tal_asrd.h); sync 3: the
@@ -1043,59 +936,36 @@ extern "C" int tal_greedy_step_fwd(tal_greedy_ctx* c, int64_t history_start, int
             }
             return TAL_EHIP;
         }
-        if (hipMemcpyAsync(c->picked_host, c->picked_dev, (size_t)(1 + S) * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            set_error("tal_greedy_step_fwd: device-to-host copy failed: %s", hipGetErrorString(hipGetLastError()));
-            return TAL_EHIP;
-        }
-        return greedy_failed_marker(c, "tal_greedy_step_fwd");
+        rc = greedy_copy_result(c, s);
+        return rc ? rc : greedy_failed_marker(c, "tal_greedy_step_fwd");
     }
     int rc = tal_embed_tokens_fwd(c->tokens + history_start, 1, U, c->emb, V, E0 > 0 ? E0 : E, E0 > 0 ? c->proj : nullptr, E, c->pe,
-                                  c->max_len, h0, stream);
+                                  c->max_len, w.h0, stream);
     if (rc) return rc;
     const bool small = small_layer_applicable(1, U, S, E, H, FF, true);
-    const float* cur = h0;
+    const float* cur = w.h0;
     for (int l = 0; l < L; ++l) {
         TAL_CHECK_ARG(c->k_cache[l] && c->vt_cache[l], "tal_greedy_step_fwd: layer %d has no cached K / V^T", l);
         if (small)
-            rc = decoder_layer_small(&c->layers[l], cur, 1, U, S, E, H, FF, nullptr, c->mem_kpm, c->k_cache[l], c->vt_cache[l], h1,
-                                     nullptr, probs + (size_t)l * H * S, ws, s, c->tickets ? &sk : nullptr, c->k_pitch, !c->no_fold);
+            rc = decoder_layer_small(&c->layers[l], greedy_layer_io(c, w, l, U), E, H, FF, !c->no_fold, nullptr, s);
         else
             rc = decoder_layer_pitched(&c->layers[l], cur, 1, U, nullptr, S, E, H, FF, nullptr, c->mem_kpm, c->k_cache[l],
-                                       c->vt_cache[l], h1, avg + (size_t)l * U * S, base, ws.total_floats * sizeof(float), stream, c->k_pitch);
+                                       c->vt_cache[l], w.h1, w.avg + (size_t)l * U * S, base, w.layer.total_floats * sizeof(float), stream, c->k_pitch);
         if (rc) return rc;
-        cur = h1;
+        cur = w.h1;
     }
-    // tied factorised LM head on the last position (models.py:243-246; system.py:355-361 reads only that row)
+    // tied factorised LM head on the last position (models.py:243-246; system.py:355-361 reads only that row); the attention rows come
+    // per head from the latency-oriented layer, head-averaged from the batched-GEMM one
     const float* hl = cur + (size_t)(U - 1) * E;
     const int K0 = E0 > 0 ? E0 : E;
-    // sync == 2 / 3: the pick kernel writes {token, row, sequence word} straight into the pinned host buffer (1 + S + 1 words)
-    // through its device alias; sync 2 polls the word here, sync 3 leaves the polling to the caller (tal_greedy_step_poll:
-    // several sessions in flight on several streams).  The sequence value is per context (one context per stream).
-    const bool host_direct = sync >= 2 && c->tickets;
-    if (host_direct && !c->picked_host_dev) {
-        void* alias = nullptr;
-        if (hipHostGetDevicePointer(&alias, c->picked_host, 0) != hipSuccess || !alias) {
-            set_error("tal_greedy_step_fwd: picked_host is not mapped pinned host memory (%s)", hipGetErrorString(hipGetLastError()));
-            return TAL_EINVAL;
-        }
-        c->picked_host_dev = reinterpret_cast<float*>(alias);
-        reinterpret_cast<volatile unsigned*>(c->picked_host)[1 + S] = 0u;      // (a recycled buffer may hold an old sequence value)
-    }
-    if (host_direct && ++c->seq == 0) ++c->seq;         // (0 is the value of a buffer nobody has written yet)
-    const unsigned seq = host_direct ? c->seq : 0u;
-    if (c->tickets && E % 16 == 0 && K0 % 8 == 0 && (reinterpret_cast<uintptr_t>(c->emb) & 15) == 0 &&
-        (!c->proj_t || (reinterpret_cast<uintptr_t>(c->proj_t) & 15) == 0)) {
-        const float* rows = small ? probs : avg + (size_t)(U - 1) * S;
-        LmPickArgs q = {};
-        q.h = hl; q.attn = rows;
-        q.layer_stride = small ? (int64_t)H * S : (int64_t)U * S;
-        q.head_stride = small ? (int64_t)S : (int64_t)0;
-        q.S = S; q.partial = pick_part; q.ticket_word = c->tickets + (TAL_GREEDY_TICKETS - 1);
-        q.out = host_direct ? c->picked_host_dev : c->picked_dev;
-        q.token_out = c->tokens + n_gen;
-        q.host_seq = host_direct ? seq : 0u;
-        q.bias = c->pick_bias;
+    const float* rows = small ? w.probs : w.avg + (size_t)(U - 1) * S;
+    const int64_t layer_stride = small ? (int64_t)H * S : (int64_t)U * S, head_stride = small ? (int64_t)S : (int64_t)0;
+    if (host_direct)
+        if ((rc = greedy_host_alias(c, "tal_greedy_step_fwd"))) return rc;
+    const unsigned seq = host_direct ? greedy_next_seq(c) : 0u;
+    if (merged_pick_ok(c)) {
+        const LmPickArgs q = lm_pick_args(hl, rows, layer_stride, head_stride, S, w.pick_part, c->tickets,
+                                          host_direct ? c->picked_host_dev : c->picked_dev, c->tokens + n_gen, seq, c->pick_bias);
         hipLaunchKernelGGL(lm_pick_kernel, dim3((unsigned)cdiv(V, LMP_ROWS)), dim3(256), (size_t)(E + K0 + LMP_ROWS) * sizeof(float), s, q,
                            E0 > 0 ? c->proj_t : nullptr, E, K0, c->emb, V, L, small ? H : 1);
         TAL_CHECK_LAUNCH("tal_greedy_step_fwd(lm head + pick)");
@@ -1111,38 +981,21 @@ extern "C" int tal_greedy_step_fwd(tal_greedy_ctx* c, int64_t history_start, int
             return TAL_EHIP;
         }
     } else {
-    if (E0 > 0) {
-        rc = tal_lm_head_fwd(hl, 1, E, E, c->proj_t, E0, c->emb, V, logits, lm_t, (size_t)E0 * sizeof(float), stream);
-    } else {
-        rc = tal_lm_head_fwd(hl, 1, E, E, nullptr, E, c->emb, V, logits, nullptr, 0, stream);
-    }
-    if (rc) return rc;
-    if (small)
-        hipLaunchKernelGGL(greedy_pick_kernel, dim3(1), dim3(256), 0, s, logits, V, probs, L, (int64_t)H * S, H, (int64_t)S, S,
+        rc = tal_lm_head_fwd(hl, 1, E, E, E0 > 0 ? c->proj_t : nullptr, K0, c->emb, V, w.logits, E0 > 0 ? w.lm_t : nullptr,
+                             E0 > 0 ? (size_t)E0 * sizeof(float) : 0, stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL(greedy_pick_kernel, dim3(1), dim3(256), 0, s, w.logits, V, rows, L, layer_stride, small ? H : 1, head_stride, S,
                            c->picked_dev, c->tokens + n_gen, c->pick_bias);
-    else
-        hipLaunchKernelGGL(greedy_pick_kernel, dim3(1), dim3(256), 0, s, logits, V, avg + (size_t)(U - 1) * S, L, (int64_t)U * S, 1,
-                           (int64_t)0, S, c->picked_dev, c->tokens + n_gen, c->pick_bias);
-    TAL_CHECK_LAUNCH("tal_greedy_step_fwd(pick)");
+        TAL_CHECK_LAUNCH("tal_greedy_step_fwd(pick)");
     }
-    if (sync) {       // (sync 2 without the merged kernels: the copy form)
-        if (hipMemcpyAsync(c->picked_host, c->picked_dev, (size_t)(1 + S) * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            set_error("tal_greedy_step_fwd: device-to-host copy failed: %s", hipGetErrorString(hipGetLastError()));
-            return TAL_EHIP;
-        }
-    }
-    return TAL_OK;
+    return sync ? greedy_copy_result(c, s) : TAL_OK;       // (sync 2 without the merged kernels: the copy form)
 }
 
 // ---- several sessions per launch -----------------------------------------------------------------------------------------
 extern "C" int tal_greedy_group_ok(const tal_greedy_ctx* c, int64_t history_start, int64_t n_gen) {
-    if (!c || !c->tickets || !c->picked_host) return 0;
+    if (!c || !c->picked_host || !merged_pick_ok(c)) return 0;
     const int64_t U = n_gen - history_start;
     if (history_start < 0 || U < 1 || U > c->max_len) return 0;
-    const int K0 = c->E0 > 0 ? c->E0 : c->E;
-    if (!(c->E % 16 == 0 && K0 % 8 == 0 && (reinterpret_cast<uintptr_t>(c->emb) & 15) == 0 && (!c->proj_t || (reinterpret_cast<uintptr_t>(c->proj_t) & 15) == 0)))
-        return 0;
     return greedy_group_ok((int)U, c->S, c->E, c->H, c->FF) ? 1 : 0;
 }
 
@@ -1152,11 +1005,8 @@ extern "C" int tal_greedy_step_multi_fwd(tal_greedy_ctx* const* ctxs, const int6
     TAL_CHECK_ARG(c0, "tal_greedy_step_multi_fwd: null context");
     const int E = c0->E, H = c0->H, FF = c0->FF, V = c0->V, E0 = c0->E0, L = c0->n_layers, K0 = E0 > 0 ? E0 : E;
     hipStream_t s = (hipStream_t)stream;
-    SessionLayerIo io[TAL_GROUP_MAX];
-    float* h0[TAL_GROUP_MAX];
-    float* h1[TAL_GROUP_MAX];
-    float* probs[TAL_GROUP_MAX];
-    float* pick_part[TAL_GROUP_MAX];
+    StepWs w[TAL_GROUP_MAX];
+    int U[TAL_GROUP_MAX];
     EmbedMulti em = {};
     int umax = 0;
     for (int i = 0; i < G; ++i) {
@@ -1173,75 +1023,46 @@ extern "C" int tal_greedy_step_multi_fwd(tal_greedy_ctx* const* ctxs, const int6
                       "tal_greedy_step_multi_fwd: session %d (prefix [%lld, %lld), window %d) does not take the merged kernels' forms: step it alone",
                       i, (long long)history_start[i], (long long)n_gen[i], c->S);
         if (int rr = greedy_reset_if_needed(c, s)) return rr;
-        const int U = (int)(n_gen[i] - history_start[i]), S = c->S;
-        if (c->workspace_bytes < tal_greedy_step_workspace_bytes(U, S, E, H, FF, V, E0, L)) {
-            set_error("tal_greedy_step_multi_fwd: session %d: workspace %zu < %zu bytes", i, c->workspace_bytes, tal_greedy_step_workspace_bytes(U, S, E, H, FF, V, E0, L));
+        U[i] = (int)(n_gen[i] - history_start[i]);
+        if (c->workspace_bytes < tal_greedy_step_workspace_bytes(U[i], c->S, E, H, FF, V, E0, L)) {
+            set_error("tal_greedy_step_multi_fwd: session %d: workspace %zu < %zu bytes", i, c->workspace_bytes, tal_greedy_step_workspace_bytes(U[i], c->S, E, H, FF, V, E0, L));
             return TAL_ENOMEM;
         }
-        // the same carving of the session's workspace as tal_greedy_step_fwd
-        float* base = reinterpret_cast<float*>(c->workspace);
-        LayerWs ws = carve(base, 1, U, S, E, H, FF);
-        float* p = base + ws.total_floats;
-        h0[i] = p; p += up64((size_t)U * E);
-        h1[i] = p; p += up64((size_t)U * E);
-        p += up64((size_t)L * U * S);                      // (avg: the batched-GEMM layer's rows, unused here)
-        probs[i] = p; p += up64((size_t)L * H * S);
-        p += up64((size_t)(E0 > 0 ? E0 : E));
-        p += up64((size_t)V);
-        DecodeScratch sk = {p, c->tickets};
-        p += up64(decode_scratch_floats(U, S, E, H));
-        pick_part[i] = p;
-        io[i].U = U; io[i].S = S; io[i].mem_kpm = c->mem_kpm; io[i].ws = ws; io[i].sk = sk; io[i].no_fold = c->no_fold != 0;
+        w[i] = carve_step(reinterpret_cast<float*>(c->workspace), c->tickets, U[i], c->S, E, H, FF, V, E0, L);
         em.tokens[i] = c->tokens + history_start[i];
-        em.out[i] = h0[i];
-        em.U[i] = U;
-        umax = U > umax ? U : umax;
-        if (!c->picked_host_dev) {
-            void* alias = nullptr;
-            if (hipHostGetDevicePointer(&alias, c->picked_host, 0) != hipSuccess || !alias) {
-                set_error("tal_greedy_step_multi_fwd: session %d: picked_host is not mapped pinned host memory (%s)", i, hipGetErrorString(hipGetLastError()));
-                return TAL_EINVAL;
-            }
-            c->picked_host_dev = reinterpret_cast<float*>(alias);
-            reinterpret_cast<volatile unsigned*>(c->picked_host)[1 + S] = 0u;
-        }
+        em.out[i] = w[i].h0;
+        em.U[i] = U[i];
+        umax = U[i] > umax ? U[i] : umax;
+        if (int rc = greedy_host_alias(c, "tal_greedy_step_multi_fwd", i)) return rc;
     }
     TAL_CHECK_ARG(K0 <= 8192, "tal_greedy_step_multi_fwd: embedding width %d too large", K0);
     hipLaunchKernelGGL(embed_multi_kernel, dim3((unsigned)umax, (unsigned)G), dim3(256), (size_t)K0 * sizeof(float), s, em, c0->emb,
                        E0 > 0 ? c0->proj : nullptr, c0->pe, V, K0, E);
     TAL_CHECK_LAUNCH("tal_greedy_step_multi_fwd(embed)");
+    const LayerDims d = layer_dims(E, H, FF);
     for (int l = 0; l < L; ++l) {
+        // (sessions on either side of the fold's row limit go through the layer as two groups of launches: each in the form its solo
+        //  step takes; both groups in the key-split / split-K forms: tal_greedy_group_ok)
+        LayerIo io[2][TAL_GROUP_MAX];
+        int n[2] = {0, 0};
         for (int i = 0; i < G; ++i) {
             const tal_greedy_ctx* c = ctxs[i];
             TAL_CHECK_ARG(c->k_cache[l] && c->vt_cache[l], "tal_greedy_step_multi_fwd: session %d, layer %d has no cached K / V^T", i, l);
-            io[i].tgt = l == 0 ? h0[i] : h1[i];
-            io[i].out = h1[i];
-            io[i].ck = c->k_cache[l];
-            io[i].k_pitch = c->k_pitch ? c->k_pitch : E;
-            io[i].cvt = c->vt_cache[l];
-            io[i].probs_last = probs[i] + (size_t)l * H * io[i].S;
+            const int f = (!c->no_fold && layer_folded(&c0->layers[l], E, U[i])) ? 1 : 0;
+            io[f][n[f]++] = greedy_layer_io(c, w[i], l, U[i]);
         }
-        const int rc = decoder_layer_small_multi(&c0->layers[l], io, G, E, H, FF, s);
-        if (rc) return rc;
+        for (int f = 1; f >= 0; --f)
+            if (n[f] > 0) {
+                const int rc = decoder_layer_walk(c0->layers[l], io[f], n[f], true, d, f == 1, true, true, nullptr, s);
+                if (rc) return rc;
+            }
     }
     ArgPack<LmPickArgs> pk;
     pk.n = G;
     for (int i = 0; i < G; ++i) {
         tal_greedy_ctx* c = ctxs[i];
-        if (++c->seq == 0) ++c->seq;
-        LmPickArgs& q = pk.a[i];
-        q = LmPickArgs{};
-        q.h = h1[i] + (size_t)(io[i].U - 1) * E;
-        q.attn = probs[i];
-        q.layer_stride = (int64_t)H * io[i].S;
-        q.head_stride = (int64_t)io[i].S;
-        q.S = io[i].S;
-        q.partial = pick_part[i];
-        q.ticket_word = c->tickets + (TAL_GREEDY_TICKETS - 1);
-        q.out = c->picked_host_dev;
-        q.token_out = c->tokens + n_gen[i];
-        q.host_seq = c->seq;
-        q.bias = c->pick_bias;
+        pk.a[i] = lm_pick_args(w[i].h1 + (size_t)(U[i] - 1) * E, w[i].probs, (int64_t)H * c->S, (int64_t)c->S, c->S, w[i].pick_part, c->tickets,
+                               c->picked_host_dev, c->tokens + n_gen[i], greedy_next_seq(c), c->pick_bias);
     }
     hipLaunchKernelGGL(lm_pick_multi_kernel, dim3((unsigned)cdiv(V, LMP_ROWS), (unsigned)G), dim3(256), (size_t)(E + K0 + LMP_ROWS) * sizeof(float), s, pk,
                        E0 > 0 ? c0->proj_t : nullptr, E, K0, c0->emb, V, L, H);
