@@ -406,16 +406,198 @@ extern "C" size_t tal_tds_workspace_bytes(const tal_tds_desc* d, int B, int64_t 
     return tal_tds_status_offset(d, B, T) + 64;
 }
 
+// Which form a stage runs in follows from two facts about it that do not depend on the form of its input; both come from the
+// descriptor, the options and the stage's input length alone.
+// ... its stride-2 resize conv can run on the matrix cores
+static bool tds_s2_mfma_ok(const tal_tds_desc* d, int B, int i, int64_t Tin, int ks, bool general, bool force_f32) {
+    return !force_f32 && !general && d->down_w_frag[i] && (int64_t)B * conv_out_len(Tin, ks) > 64 &&
+           gconv_f16x3_weight_bytes(d->channels[i], d->channels[i + 1], d->groups, 2) > 0 && gconv_f16x3_fits(Tin, d->channels[i]);
+}
+// ... its TDSBlocks can keep every activation in the hi / lo split form (`fp32_only`: the exact mode or option tds_fp32_activations)
+static bool tds_blocks_split_ok(const tal_tds_desc* d, int B, int i, int64_t Tin, int ks, bool general, bool fp32_only) {
+    if (fp32_only || general || d->depths[i] == 0) return false;
+    const int c = d->channels[i + 1];
+    const int64_t To = conv_out_len(Tin, ks);
+    if ((int64_t)B * To <= 128 || c % 160 != 0 || c % 32 != 0 || !gconv_f16x3_fits(To, c) || gconv_f16x3_weight_bytes(c, c, d->groups, 1) == 0) return false;
+    for (int j = 0; j < d->depths[i]; ++j)
+        if (!d->blocks[i][j].fc0_w_split || !d->blocks[i][j].fc3_w_split || !d->blocks[i][j].conv_w_frag) return false;
+    return true;
+}
+
+// the resize conv of stage i, cur -> a, in the form the stage runs in (allsplit: a receives the split form only)
+static int tds_launch_resize(const tal_tds_desc* d, int i, const float* cur, bool cur_split, const float* x_mean, int B, int64_t Tc, int ks, bool general,
+                             bool s2_mfma, bool allsplit, float* a, hipStream_t s, int* range_flag) {
+    const int cin = d->channels[i], c = d->channels[i + 1];
+    if (general) return launch_gconv_s2_k(cur, d->down_w[i], d->down_b[i], B, Tc, cin, c, d->groups, ks, a, s);
+    // on the matrix cores when the fragments are there (10 -> 14, 14 -> 18 per group); it pays from ~a hundred output steps on: 358 steps
+    // of 18 channels per group take 13 us against 57
+    if (s2_mfma)
+        return launch_gconv_s2_f16x3(cur, d->down_w_frag[i], d->down_b[i], B, Tc, cin, c, d->groups, allsplit ? nullptr : a, s, range_flag, cur_split,
+                                     allsplit ? a : nullptr);
+    return launch_gconv_s2(cur, d->down_w[i], d->down_b[i], B, Tc, cin, c, d->groups, allsplit ? nullptr : a, s, allsplit ? a : nullptr,
+                           allsplit ? range_flag : nullptr, i == 0 ? x_mean : nullptr);
+}
+
+// the two dense layers of a block: h = relu(fc0(xin)), out = x1 + rw * fc3(h).  fp32 kernels, or (f16x3) the fp16x3 form on xin = the split
+// form of x1, fc0 writing h already split; in an all-split stage x1 is split as well and fc3 writes the split form where out_split
+static int tds_launch_dense(const tal_tds_block_w& bw, bool f16x3, bool allsplit, const float* xin, const float* x1, float* h, float* outp, bool out_split,
+                            int64_t M, int c, float* skws, hipStream_t s, int* range_flag) {
+    const size_t skb = gemm_splitk_ws_bytes();
+    int rc;
+    if (f16x3) {
+        rc = launch_linear_f16x3(xin, bw.fc0_w_split, bw.fc0_b, nullptr, 0.f, 1, M, c, c, h, 1, skws, skb, s, range_flag);
+        if (rc) return rc;
+        return launch_linear_f16x3(h, bw.fc3_w_split, bw.fc3_b, x1, bw.resweight, 2, M, c, c, outp, out_split ? 1 : 0, skws, skb, s,
+                                   allsplit ? range_flag : nullptr, allsplit ? 1 : 0);
+    }
+    rc = launch_linear_ws(xin, bw.fc0_w, bw.fc0_b, nullptr, 0.f, 1, M, c, c, h, skws, skb, s);
+    if (rc) return rc;
+    return launch_linear_ws(h, bw.fc3_w, bw.fc3_b, x1, bw.resweight, 2, M, c, c, outp, skws, skb, s);
+}
+
+// The one walk over the stages: it decides which form every layer runs in and, with `launch`, launches it.  *y_split: the form y ends in.
+// Without `launch` it is the same chain of decisions and nothing else -- no device call, no check of the weights -- and x, y and the
+// workspace serve as addresses only (the 1 -> 10 channel kernels ask for a 16-byte aligned input): nothing is read through them.
+static int tds_walk(const tal_tds_desc* d, const float* x, const float* x_mean, int B, int64_t T, float* y, void* workspace, hipStream_t s,
+                    bool launch, bool* y_split) {
+    const size_t nf = tds_buf_floats(d, B, T);
+    float* buf[4];
+    for (int q = 0; q < 4; ++q) buf[q] = reinterpret_cast<float*>(workspace) + q * nf;
+    float* skws = reinterpret_cast<float*>(workspace) + 4 * nf;   // split-K scratch of the dense layers
+    // status word: raised by any kernel that turns an fp32 value outside the finite fp16 range into hi / lo halves
+    int* range_flag = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + tal_tds_status_offset(d, B, T));
+    // four rotating buffers; `ia` = index of the buffer holding the live activations (-1: caller's x).
+    // No launch ever reads and writes the same buffer (workgroups read halos of their neighbours).
+    //
+    // Activation format.  Long inputs run a stage with every inter-kernel activation in the hi / lo SPLIT form of the
+    // fp16x3 dense layers (same bytes as fp32; the exact value is hi + lo * 2^-11, 22 mantissa bits): the resize conv writes
+    // it, the TDSBlock conv reads it (no conversion arithmetic in its slab phase) and writes it, fc0 reads / writes it, fc3
+    // reads it twice (operand and residual) and writes it for the next block.  No fp32 copy of an activation and no
+    // separate split pass exist inside such a stage: 7 activation-sized transfers per block instead of 10.  Short inputs,
+    // odd widths and the exact mode keep fp32 activations (the kernels below the `else`).
+    const bool force_f32 = opt(OPT_TDS_EXACT_F32) != 0 || (d->flags & TAL_TDS_EXACT_F32) != 0;
+    const bool fp32_only = force_f32 || opt(OPT_TDS_FP32_ACTIVATIONS) != 0;
+    const int ks = tds_ksize(d);
+    // k != 21 (or the option gconv_general): every grouped conv on the exact fp32 any-k kernels; the dense layers keep their forms
+    const bool general = tds_general(d);
+    const float* cur = x;
+    bool cur_split = false;      // the live activations are in the split form
+    int ia = -1;
+    int64_t Tc = T;
+    // the two facts of the stage the walk enters next: the stage in front of it chooses its output form by them
+    bool s2_mfma = tds_s2_mfma_ok(d, B, 0, T, ks, general, force_f32), blocks_split = tds_blocks_split_ok(d, B, 0, T, ks, general, fp32_only);
+    for (int i = 0; i < d->n_stages; ++i) {
+        const int cin = d->channels[i], c = d->channels[i + 1];
+        const int64_t To = conv_out_len(Tc, ks);
+        const bool last_stage = i == d->n_stages - 1;
+        const int64_t M = (int64_t)B * To;
+        // all-split: the blocks can, and the resize conv can write the split form from what it reads -- a matrix-core kernel (a split
+        // input in 32-channel blocks) or the 1 -> 10 channel kernel (fp32 input, 16-byte aligned)
+        const bool allsplit = blocks_split && (s2_mfma ? (!cur_split || cin % 32 == 0) : (!cur_split && gconv_s2_can_split(cin, c, d->groups, cur)));
+        // what the next consumer of this stage's output can read: the next stage's resize conv takes the split form only if
+        // that stage runs all-split itself through a matrix-core resize conv
+        const bool next_s2_mfma = !last_stage && tds_s2_mfma_ok(d, B, i + 1, To, ks, general, force_f32);
+        const bool next_blocks_split = !last_stage && tds_blocks_split_ok(d, B, i + 1, To, ks, general, fp32_only);
+        const bool next_split = c % 32 == 0 && next_s2_mfma && next_blocks_split;
+        // resize conv: cur -> a (a buffer other than cur's)
+        const int io = (ia + 1) % 4;
+        float* a = (last_stage && d->depths[i] == 0) ? y : buf[io];
+        // option gconv_c1_fuse (round 6, off by default): the first stage's resize conv (1 mel bin -> 10 channels per group) runs INSIDE the
+        // first TDSBlock conv's launch -- its output is computed straight into that kernel's LDS slab and never touches memory.  Bit-identical
+        // and one launch + 1.15 GB of traffic per hour of audio less, but the conv's 3 G multiply-adds cost the same ~0.25 ms inside the
+        // matrix-core kernel as in a launch of their own (profiles/r6_gconv_c1_fusion.txt): measured, kept for the record, not the default
+        const bool c1_fused = allsplit && i == 0 && !s2_mfma && opt(OPT_GCONV_C1_FUSE) && !opt(OPT_GCONV_C1_GENERIC) &&
+                              gconv_c1_res_fusable(cin, c, d->groups, cur);
+        if (launch && !c1_fused) {
+            TAL_CHECK_ARG(allsplit || !cur_split, "tal_tds_fwd: internal: stage %d would read a split activation through an fp32 kernel", i);
+            const int rc = tds_launch_resize(d, i, cur, cur_split, x_mean, B, Tc, ks, general, s2_mfma, allsplit, a, s, range_flag);
+            if (rc) return rc;
+        }
+        ia = io;
+        cur_split = allsplit;
+        for (int j = 0; j < d->depths[i]; ++j) {
+            const tal_tds_block_w& bw = d->blocks[i][j];
+            const bool last_block = j == d->depths[i] - 1;
+            float* outp = (last_stage && last_block) ? y : buf[ia];
+            // the block's output stays split inside an all-split stage, and behind it for a consumer that reads the form: the next stage, or
+            // (TAL_TDS_OUT_SPLIT) the caller's -- the diarization head's embedding layer takes the split form itself
+            const bool out_split = allsplit && (!last_block || next_split || (last_stage && (d->flags & TAL_TDS_OUT_SPLIT) != 0));
+            if (launch) {
+                TAL_CHECK_ARG(bw.conv_w && bw.conv_b && bw.fc0_w && bw.fc0_b && bw.fc3_w && bw.fc3_b, "tal_tds_fwd: null weight in block %d.%d", i, j);
+                float* x1 = buf[(ia + 1) % 4];
+                float* h = buf[(ia + 2) % 4];
+                float* x1s = buf[(ia + 3) % 4];
+                // x1 = x + rw * relu(gconv(x)): a -> x1; h = relu(fc0(x1)); out = x1 + rw * fc3(h): h (+res x1) -> a's buffer (dead since the gconv)
+                int rc;
+                if (allsplit) {
+                    if (c1_fused && j == 0)
+                        rc = launch_gconv_c1_res_f16x3(cur, d->down_w[i], d->down_b[i], x_mean, bw.conv_w_frag, bw.conv_b, bw.resweight, B, Tc, d->groups, x1, s, range_flag);
+                    else
+                        rc = launch_gconv_res_f16x3(a, bw.conv_w_frag, bw.conv_b, bw.resweight, B, To, c, d->groups, nullptr, x1, s, range_flag, true);
+                    if (!rc) rc = tds_launch_dense(bw, true, true, x1, x1, h, outp, out_split, M, c, skws, s, range_flag);
+                } else {
+                    const bool f16x3 = !force_f32 && bw.fc0_w_split && bw.fc3_w_split && M > 128 && c % 160 == 0;
+                    const bool conv_mfma = !force_f32 && !general && M > 64 && bw.conv_w_frag && gconv_f16x3_weight_bytes(c, c, d->groups, 1) > 0 && gconv_f16x3_fits(To, c);
+                    const bool fuse_split = opt(OPT_GCONV_FUSE_SPLIT) != 0;
+                    if (general)
+                        rc = launch_gconv_res_k(a, bw.conv_w, bw.conv_b, bw.resweight, B, To, c, d->groups, ks, x1, s);
+                    else if (conv_mfma)
+                        rc = launch_gconv_res_f16x3(a, bw.conv_w_frag, bw.conv_b, bw.resweight, B, To, c, d->groups, x1, (fuse_split && f16x3) ? x1s : nullptr, s,
+                                                    range_flag);
+                    else
+                        rc = launch_gconv_res(a, bw.conv_w, bw.conv_b, bw.resweight, B, To, c, d->groups, x1, s);
+                    // the two dense layers in the fp16x3 form: x1 is split once (by the conv, or by a pass of its own)
+                    if (!rc && f16x3 && !(conv_mfma && fuse_split)) rc = launch_split_f16x3(x1, x1s, M, c, s, range_flag);
+                    if (!rc) rc = tds_launch_dense(bw, f16x3, false, f16x3 ? x1s : x1, x1, h, outp, false, M, c, skws, s, range_flag);
+                }
+                if (rc) return rc;
+            }
+            a = outp;
+            cur_split = out_split;
+        }
+        cur = a;
+        Tc = To;
+        s2_mfma = next_s2_mfma;
+        blocks_split = next_blocks_split;
+    }
+    *y_split = cur_split;
+    return TAL_OK;
+}
+
 static int tds_fwd_impl(const tal_tds_desc* d, const float* x, const float* x_mean, int B, int64_t T, float* y, void* workspace,
-                        size_t workspace_bytes, void* stream);
-static bool tds_last_stage_allsplit(const tal_tds_desc* d, int B, int64_t T, const float* x0);
+                        size_t workspace_bytes, void* stream) {
+    int rc = check_desc(d);
+    if (rc) return rc;
+    TAL_CHECK_ARG(x && y && workspace, "tal_tds_fwd: null pointer");
+    TAL_CHECK_ARG(B > 0 && tal_tds_out_len(d, T) > 0, "tal_tds_fwd: T=%lld too short for %d stride-2 k=%d stages", (long long)T, d->n_stages, tds_ksize(d));
+    if (workspace_bytes < tal_tds_workspace_bytes(d, B, T)) {
+        set_error("tal_tds_fwd: workspace %zu < %zu bytes", workspace_bytes, tal_tds_workspace_bytes(d, B, T));
+        return TAL_ENOMEM;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // the form y will be written in, from the real buffers and the options of THIS call (tal_tds_out_split is a prediction made earlier,
+    // for aligned ones): the walk without launches; recorded in word 1 of the status block, where the caller that consumes y in the split
+    // form checks it.  (Without TAL_TDS_OUT_SPLIT y is fp32 whatever the stages do: no walk needed.)
+    bool y_split_out = false;
+    if (d->flags & TAL_TDS_OUT_SPLIT) tds_walk(d, x, x_mean, B, T, y, workspace, s, false, &y_split_out);
+    int* status = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + tal_tds_status_offset(d, B, T));
+    clear_status_kernel<<<1, 16, 0, s>>>(status, y_split_out ? 1 : 0);
+    if (hipGetLastError() != hipSuccess) {
+        set_error("tal_tds_fwd: cannot clear the status word");
+        return TAL_EHIP;
+    }
+    return tds_walk(d, x, x_mean, B, T, y, workspace, s, true, &y_split_out);
+}
 
 // 1: a call with TAL_TDS_OUT_SPLIT in d->flags leaves y in the hi / lo split form (the last stage runs all-split: long inputs on
 // the fp16x3 kernels); 0: y is fp32 as always (short inputs, odd widths, the exact mode)
 extern "C" int tal_tds_out_split(const tal_tds_desc* d, int B, int64_t T) {
     if (check_desc(d) || B <= 0 || tal_tds_out_len(d, T) <= 0 || !(d->flags & TAL_TDS_OUT_SPLIT)) return 0;
-    // (a PREDICTION for a 16-byte aligned x under the options in force now; the call records what it did in its status block)
-    return tds_last_stage_allsplit(d, B, T, reinterpret_cast<const float*>(static_cast<uintptr_t>(16))) ? 1 : 0;
+    // (a PREDICTION for 16-byte aligned buffers under the options in force now; the call records what it did in its status block)
+    float* const aligned = reinterpret_cast<float*>(static_cast<uintptr_t>(16));
+    bool y_split = false;
+    tds_walk(d, aligned, nullptr, B, T, aligned, aligned, nullptr, false, &y_split);
+    return y_split ? 1 : 0;
 }
 
 extern "C" int tal_tds_fwd(const tal_tds_desc* d, const float* x, int B, int64_t T, float* y, void* workspace,
@@ -436,198 +618,6 @@ extern "C" int tal_tds_premean_fwd(const tal_tds_desc* d, const float* x, const 
     TAL_CHECK_ARG(tal_tds_premean_ok(d, x), "tal_tds_premean_fwd: the first resize conv of this stack (%d -> %d channels, %d groups) has no mean-folding "
                   "kernel: subtract the mean (tal_subtract_scalar) and call tal_tds_fwd", d->channels[0], d->channels[1], d->groups);
     return tds_fwd_impl(d, x, x_mean, B, T, y, workspace, workspace_bytes, stream);
-}
-
-// Which form a stage of the stack runs in is decided from the descriptor and the shapes alone (tal_tds_fwd and tal_tds_out_split share it).
-static bool tds_s2_mfma_ok(const tal_tds_desc* d, int B, int i, int64_t Tin, bool force_f32) {       // stride-2 resize conv of stage i on the matrix cores
-    return !force_f32 && !tds_general(d) && d->down_w_frag[i] && (int64_t)B * conv_out_len(Tin, 21) > 64 &&
-           gconv_f16x3_weight_bytes(d->channels[i], d->channels[i + 1], d->groups, 2) > 0 && gconv_f16x3_fits(Tin, d->channels[i]);
-}
-static bool tds_stage_allsplit(const tal_tds_desc* d, int B, int64_t T, int i, const float* xin, bool in_split, bool force_f32, bool no_allsplit) {
-    if (force_f32 || no_allsplit || i >= d->n_stages || d->depths[i] == 0 || tds_general(d)) return false;
-    const int c = d->channels[i + 1], cin = d->channels[i];
-    int64_t Tin = T;
-    for (int q = 0; q < i; ++q) Tin = conv_out_len(Tin, 21);
-    const int64_t To = conv_out_len(Tin, 21), M = (int64_t)B * To;
-    if (M <= 128 || c % 160 != 0 || c % 32 != 0 || !gconv_f16x3_fits(To, c) || gconv_f16x3_weight_bytes(c, c, d->groups, 1) == 0) return false;
-    for (int j = 0; j < d->depths[i]; ++j)
-        if (!d->blocks[i][j].fc0_w_split || !d->blocks[i][j].fc3_w_split || !d->blocks[i][j].conv_w_frag) return false;
-    // the resize conv must be able to write the split form: the 1 -> 10 channel kernel or a matrix-core kernel
-    if (tds_s2_mfma_ok(d, B, i, Tin, force_f32)) return !in_split || cin % 32 == 0;
-    return !in_split && gconv_s2_can_split(cin, c, d->groups, xin);
-}
-// the last stage's form, with the input form it will see (the previous stage's output is split iff that stage and the matrix-core
-// resize conv between them allow it: the same chain of decisions tds_fwd_impl makes)
-static bool tds_last_stage_allsplit(const tal_tds_desc* d, int B, int64_t T, const float* x0) {
-    const bool force_f32 = opt(OPT_TDS_EXACT_F32) != 0 || (d->flags & TAL_TDS_EXACT_F32) != 0;
-    const bool no_allsplit = opt(OPT_TDS_FP32_ACTIVATIONS) != 0;
-    bool cur_split = false;
-    int64_t Tc = T;
-    bool allsplit = false;
-    for (int i = 0; i < d->n_stages; ++i) {
-        const int64_t To = conv_out_len(Tc, tds_ksize(d));
-        // (stage 0 reads the caller's fp32 x: its alignment matters to the 1 -> 10 kernel; later stages read workspace buffers)
-        allsplit = tds_stage_allsplit(d, B, T, i, i == 0 ? x0 : reinterpret_cast<const float*>(static_cast<uintptr_t>(16)), cur_split, force_f32, no_allsplit);
-        const bool last_stage = i == d->n_stages - 1;
-        const bool next_split = !last_stage && d->channels[i + 1] % 32 == 0 && tds_s2_mfma_ok(d, B, i + 1, To, force_f32) &&
-                                tds_stage_allsplit(d, B, T, i + 1, nullptr, true, force_f32, no_allsplit);
-        cur_split = d->depths[i] > 0 && allsplit && next_split;
-        Tc = To;
-    }
-    return allsplit && d->depths[d->n_stages - 1] > 0 && d->channels[d->n_stages] % 32 == 0;
-}
-
-static int tds_fwd_impl(const tal_tds_desc* d, const float* x, const float* x_mean, int B, int64_t T, float* y, void* workspace,
-                        size_t workspace_bytes, void* stream) {
-    int rc = check_desc(d);
-    if (rc) return rc;
-    TAL_CHECK_ARG(x && y && workspace, "tal_tds_fwd: null pointer");
-    TAL_CHECK_ARG(B > 0 && tal_tds_out_len(d, T) > 0, "tal_tds_fwd: T=%lld too short for %d stride-2 k=%d stages", (long long)T, d->n_stages, tds_ksize(d));
-    if (workspace_bytes < tal_tds_workspace_bytes(d, B, T)) {
-        set_error("tal_tds_fwd: workspace %zu < %zu bytes", workspace_bytes, tal_tds_workspace_bytes(d, B, T));
-        return TAL_ENOMEM;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nf = tds_buf_floats(d, B, T);
-    float* buf[4];
-    for (int q = 0; q < 4; ++q) buf[q] = reinterpret_cast<float*>(workspace) + q * nf;
-    float* skws = reinterpret_cast<float*>(workspace) + 4 * nf;   // split-K scratch of the dense layers
-    const bool force_f32 = opt(OPT_TDS_EXACT_F32) != 0 || (d->flags & TAL_TDS_EXACT_F32) != 0;
-    // status word: raised by any kernel that turns an fp32 value outside the finite fp16 range into hi / lo halves
-    int* range_flag = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + tal_tds_status_offset(d, B, T));
-    // the form y will be written in, from the real x and the options of THIS call (tal_tds_out_split is a prediction made earlier,
-    // for an aligned x): recorded in word 1 of the status block, where the caller that consumes y in the split form checks it
-    const bool y_split_out = (d->flags & TAL_TDS_OUT_SPLIT) != 0 && tds_last_stage_allsplit(d, B, T, x);
-    clear_status_kernel<<<1, 16, 0, s>>>(range_flag, y_split_out ? 1 : 0);
-    if (hipGetLastError() != hipSuccess) {
-        set_error("tal_tds_fwd: cannot clear the status word");
-        return TAL_EHIP;
-    }
-    // four rotating buffers; `ia` = index of the buffer holding the live activations (-1: caller's x).
-    // No launch ever reads and writes the same buffer (workgroups read halos of their neighbours).
-    //
-    // Activation format.  Long inputs run a stage with every inter-kernel activation in the hi / lo SPLIT form of the
-    // fp16x3 dense layers (same bytes as fp32; the exact value is hi + lo * 2^-11, 22 mantissa bits): the resize conv writes
-    // it, the TDSBlock conv reads it (no conversion arithmetic in its slab phase) and writes it, fc0 reads / writes it, fc3
-    // reads it twice (operand and residual) and writes it for the next block.  No fp32 copy of an activation and no
-    // separate split pass exist inside such a stage: 7 activation-sized transfers per block instead of 10.  Short inputs,
-    // odd widths and the exact mode keep fp32 activations (the kernels below the `else`).
-    const bool no_allsplit = opt(OPT_TDS_FP32_ACTIVATIONS) != 0;
-    auto s2_mfma_ok = [&](int i, int64_t Tin) { return tds_s2_mfma_ok(d, B, i, Tin, force_f32); };
-    auto stage_allsplit = [&](int i, const float* xin, bool in_split) { return tds_stage_allsplit(d, B, T, i, xin, in_split, force_f32, no_allsplit); };
-    const float* cur = x;
-    bool cur_split = false;
-    int ia = -1;
-    int64_t Tc = T;
-    const int ks = tds_ksize(d);
-    // k != 21 (or the option gconv_general): every grouped conv on the exact fp32 any-k kernels; the dense layers keep their forms
-    const bool general = tds_general(d);
-    for (int i = 0; i < d->n_stages; ++i) {
-        const int cin = d->channels[i], c = d->channels[i + 1];
-        const int64_t To = conv_out_len(Tc, ks);
-        const bool last_stage = i == d->n_stages - 1;
-        const int64_t M = (int64_t)B * To;
-        const bool allsplit = stage_allsplit(i, cur, cur_split);
-        // resize conv: cur -> a (a buffer other than cur's)
-        const int io = (ia + 1) % 4;
-        float* a = (last_stage && d->depths[i] == 0) ? y : buf[io];
-        // option gconv_c1_fuse (round 6, off by default): the first stage's resize conv (1 mel bin -> 10 channels per group) runs INSIDE the
-        // first TDSBlock conv's launch -- its output is computed straight into that kernel's LDS slab and never touches memory.  Bit-identical
-        // and one launch + 1.15 GB of traffic per hour of audio less, but the conv's 3 G multiply-adds cost the same ~0.25 ms inside the
-        // matrix-core kernel as in a launch of their own (profiles/r6_gconv_c1_fusion.txt): measured, kept for the record, not the default
-        const bool c1_fused = !general && allsplit && i == 0 && !cur_split && !s2_mfma_ok(i, Tc) && d->depths[i] > 0 && opt(OPT_GCONV_C1_FUSE) &&
-                              !opt(OPT_GCONV_C1_GENERIC) && gconv_c1_res_fusable(cin, c, d->groups, cur);
-        if (c1_fused) {
-            rc = TAL_OK;
-        } else if (allsplit) {
-            if (s2_mfma_ok(i, Tc))
-                rc = launch_gconv_s2_f16x3(cur, d->down_w_frag[i], d->down_b[i], B, Tc, cin, c, d->groups, nullptr, s, range_flag, cur_split, a);
-            else
-                rc = launch_gconv_s2(cur, d->down_w[i], d->down_b[i], B, Tc, cin, c, d->groups, nullptr, s, a, range_flag, i == 0 ? x_mean : nullptr);
-        } else {
-            TAL_CHECK_ARG(!cur_split, "tal_tds_fwd: internal: stage %d would read a split activation through an fp32 kernel", i);
-            // stride-2 resize conv: on the matrix cores when the fragments are there (10 -> 14, 14 -> 18 per group); it pays from
-            // ~a hundred output steps on: 358 steps of 18 channels per group take 13 us against 57
-            if (general)
-                rc = launch_gconv_s2_k(cur, d->down_w[i], d->down_b[i], B, Tc, cin, c, d->groups, ks, a, s);
-            else if (s2_mfma_ok(i, Tc))
-                rc = launch_gconv_s2_f16x3(cur, d->down_w_frag[i], d->down_b[i], B, Tc, cin, c, d->groups, a, s, range_flag);
-            else
-                rc = launch_gconv_s2(cur, d->down_w[i], d->down_b[i], B, Tc, cin, c, d->groups, a, s, nullptr, nullptr, i == 0 ? x_mean : nullptr);
-        }
-        if (rc) return rc;
-        ia = io;
-        // what the next consumer of this stage's output can read: the next stage's resize conv takes the split form only if
-        // that stage runs all-split itself through a matrix-core resize conv
-        const bool next_split = !last_stage && d->channels[i + 1] % 32 == 0 && s2_mfma_ok(i + 1, To) && stage_allsplit(i + 1, nullptr, true);
-        for (int j = 0; j < d->depths[i]; ++j) {
-            const tal_tds_block_w& bw = d->blocks[i][j];
-            TAL_CHECK_ARG(bw.conv_w && bw.conv_b && bw.fc0_w && bw.fc0_b && bw.fc3_w && bw.fc3_b, "tal_tds_fwd: null weight in block %d.%d", i, j);
-            float* x1 = buf[(ia + 1) % 4];
-            float* h = buf[(ia + 2) % 4];
-            float* x1s = buf[(ia + 3) % 4];
-            const bool last_block = j == d->depths[i] - 1;
-            float* outp = (last_stage && last_block) ? y : buf[ia];
-            if (allsplit) {
-                // x1 = x + rw * relu(gconv(x)): a (split) -> x1 (split); h = relu(fc0(x1)) (split); out = x1 + rw * fc3(h)
-                if (c1_fused && j == 0)
-                    rc = launch_gconv_c1_res_f16x3(cur, d->down_w[i], d->down_b[i], x_mean, bw.conv_w_frag, bw.conv_b, bw.resweight, B, Tc, d->groups, x1, s, range_flag);
-                else
-                    rc = launch_gconv_res_f16x3(a, bw.conv_w_frag, bw.conv_b, bw.resweight, B, To, c, d->groups, nullptr, x1, s, range_flag, true);
-                if (rc) return rc;
-                rc = launch_linear_f16x3(x1, bw.fc0_w_split, bw.fc0_b, nullptr, 0.f, 1, M, c, c, h, 1, skws, gemm_splitk_ws_bytes(), s, range_flag);
-                if (rc) return rc;
-                // (TAL_TDS_OUT_SPLIT: the caller's consumer -- the diarization head's embedding layer -- takes the split form itself)
-                const bool out_split = !last_block || next_split || (last_stage && (d->flags & TAL_TDS_OUT_SPLIT) != 0);
-                rc = launch_linear_f16x3(h, bw.fc3_w_split, bw.fc3_b, x1, bw.resweight, 2, M, c, c, outp, out_split ? 1 : 0, skws,
-                                         gemm_splitk_ws_bytes(), s, range_flag, 1);
-                if (rc) return rc;
-                a = outp;
-                cur_split = out_split;
-                continue;
-            }
-            const bool f16x3 = !force_f32 && bw.fc0_w_split && bw.fc3_w_split && M > 128 && c % 160 == 0;
-            const bool conv_mfma = !force_f32 && !general && M > 64 && bw.conv_w_frag && gconv_f16x3_weight_bytes(c, c, d->groups, 1) > 0 && gconv_f16x3_fits(To, c);
-            // x1 = x + rw * relu(gconv(x))            : a -> x1
-            const bool fuse_split = opt(OPT_GCONV_FUSE_SPLIT) != 0;
-            if (general)
-                rc = launch_gconv_res_k(a, bw.conv_w, bw.conv_b, bw.resweight, B, To, c, d->groups, ks, x1, s);
-            else if (conv_mfma)
-                rc = launch_gconv_res_f16x3(a, bw.conv_w_frag, bw.conv_b, bw.resweight, B, To, c, d->groups, x1, (fuse_split && f16x3) ? x1s : nullptr, s,
-                                            range_flag);
-            else
-                rc = launch_gconv_res(a, bw.conv_w, bw.conv_b, bw.resweight, B, To, c, d->groups, x1, s);
-            if (rc) return rc;
-            if (f16x3) {
-                // the two dense layers in the fp16x3 form: x1 is split once, fc0 writes its output already split
-                if (!(conv_mfma && fuse_split)) rc = launch_split_f16x3(x1, x1s, M, c, s, range_flag);
-                if (rc) return rc;
-                rc = launch_linear_f16x3(x1s, bw.fc0_w_split, bw.fc0_b, nullptr, 0.f, 1, M, c, c, h, 1, skws, gemm_splitk_ws_bytes(), s, range_flag);
-                if (rc) return rc;
-                rc = launch_linear_f16x3(h, bw.fc3_w_split, bw.fc3_b, x1, bw.resweight, 2, M, c, c, outp, 0, skws,
-                                         gemm_splitk_ws_bytes(), s);
-                if (rc) return rc;
-            } else {
-                // h = relu(fc0(x1))                        : x1 -> h
-                rc = launch_linear_ws(x1, bw.fc0_w, bw.fc0_b, nullptr, 0.f, 1, M, c, c, h, skws, gemm_splitk_ws_bytes(), s);
-                if (rc) return rc;
-                // x2 = x1 + rw * fc3(h)                    : h (+res x1) -> a's buffer (dead since the gconv)
-                rc = launch_linear_ws(h, bw.fc3_w, bw.fc3_b, x1, bw.resweight, 2, M, c, c, outp, skws,
-                                      gemm_splitk_ws_bytes(), s);
-                if (rc) return rc;
-            }
-            a = outp;
-            cur_split = false;
-        }
-        if (d->depths[i] == 0) cur_split = false;
-        cur = a;
-        Tc = To;
-    }
-    if (cur_split != y_split_out) {      // (the two decision chains disagree: never silently)
-        set_error("tal_tds_fwd: internal: y was written %s but the status block says %s", cur_split ? "split" : "fp32", y_split_out ? "split" : "fp32");
-        return TAL_EINVAL;
-    }
-    return TAL_OK;
 }
 
 // ---------------------------------------------------------------------------------------
