@@ -622,13 +622,18 @@ int tal_beam_topk(const float* logprobs, const float* row_score, const uint8_t* 
  *   pool: out[n] = sum_s attn[n,s] * feat[window(n)][s]; half_mode != 0 reproduces the reference's arithmetic:
  *         attention and features rounded to fp16 (`.half()`), fp32 accumulation, fp16-rounded result
  *   vote: out_id[n] = speaker id with the largest summed attention inside the window (lowest position on ties;
- *         out_weight [N] = that sum, may be NULL)
+ *         out_weight [N] = that sum, may be NULL); an empty window gives out_id = -1 and out_weight = -infinity (the
+ *         maximum over no candidates).  S <= 8192 (S * 8 bytes of LDS), TAL_EINVAL with a message beyond.
  *   vote_groups: the same vote over the tokens [group_offsets[g], group_offsets[g+1]) of each of G groups (one word,
  *         :150-196): float64 sums; half_mode rounds the attention to fp16 first (then the sums are exact and
  *         order-independent); ties go to the id whose first appearance is LAST (sorted(...)[-1] over a dict in
- *         insertion order); empty group -> -1.  ids outside [0, num_ids) are ignored; num_ids * 12 bytes of LDS.
+ *         insertion order); empty group (no tokens, empty windows, or no id inside [0, num_ids)) -> out_id = -1 and
+ *         out_weight = 0.  ids outside [0, num_ids) are ignored; num_ids * 12 + 8 bytes of LDS: num_ids <= 13631,
+ *         TAL_EINVAL with a message beyond (the same limit holds for majority_vote).
  *   majority_vote: most frequent id in the python slice ids[ranges[2g] : ranges[2g+1]] (:330-333,
- *         Counter.most_common(1): ties go to the id that appears first); empty range -> -1.
+ *         Counter.most_common(1): ties go to the id that appears first); out_count [G] = its count (may be NULL);
+ *         empty range -> out_id = -1 and out_count = 0.
+ *   N == 0 / G == 0 return TAL_OK and write nothing.
  * ------------------------------------------------------------------ */
 int tal_attn_pool_fwd(const float* attn, const int64_t* chunk_start, const float* feat, int64_t T,
                       int E, int N, int S, int half_mode, float* out, void* stream);

@@ -89,8 +89,8 @@ __global__ __launch_bounds__(256) void attn_vote_kernel(const float* __restrict_
     if (threadIdx.x == 0) {
         for (int q = 1; q < 4; ++q)
             if (bw[q] > best || (bw[q] == best && bpos[q] < bp)) { best = bw[q]; bi = bid[q]; bp = bpos[q]; }
-        out_id[n] = bi;
-        if (out_w) out_w[n] = best;
+        out_id[n] = bi;                 // -1: empty window
+        if (out_w) out_w[n] = best;     // (-inf then: the maximum over no candidates)
     }
 }
 
@@ -171,18 +171,35 @@ __global__ __launch_bounds__(256) void group_vote_kernel(const float* __restrict
     }
 }
 
+// A launch gets 64 KB of LDS, static and dynamic together, unless the kernel's dynamic limit has been raised.  The static part
+// (the merge arrays bw / bid / bpos) counts: a dynamic size just under 64 KB is already over the limit with it.  Done once per
+// kernel, for the largest dynamic size its entry point admits (racing first calls set the same value).
+static int reserve_lds(const char* what, const void* kern, size_t max_dyn, bool& done) {
+    if (done) return TAL_OK;
+    hipFuncAttributes fa;
+    const hipError_t e = hipFuncGetAttributes(&fa, kern);
+    if (e != hipSuccess) {
+        set_error("%s: hipFuncGetAttributes failed: %s", what, hipGetErrorString(e));
+        return TAL_EHIP;
+    }
+    if (fa.sharedSizeBytes + max_dyn > 64 * 1024 &&
+        hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_dyn) != hipSuccess) {
+        set_error("%s: cannot reserve %zu + %zu bytes of LDS", what, (size_t)fa.sharedSizeBytes, max_dyn);
+        return TAL_EHIP;
+    }
+    done = true;
+    return TAL_OK;
+}
+
 template <int MODE>
 static int launch_group_vote(const char* what, const float* attn, const int64_t* cs, const int32_t* ids, int64_t T, int S,
                              const int64_t* seg, int G, int num_ids, int half_mode, int32_t* out_id, double* out_w,
                              hipStream_t s) {
-    const size_t lds = (size_t)num_ids * 12 + 8;
-    TAL_CHECK_ARG(lds <= 160 * 1024 - 256, "%s: %d speaker ids need %zu bytes of LDS (max 160 KB)", what, num_ids, lds);
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&group_vote_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess) {
-        set_error("%s: cannot reserve %zu bytes of LDS", what, lds);
-        return TAL_EHIP;
-    }
+    const size_t lds = (size_t)num_ids * 12 + 8, lds_max = 160 * 1024 - 256;   // (256 bytes cover the kernel's 64 static ones)
+    TAL_CHECK_ARG(lds <= lds_max, "%s: %d speaker ids need %zu bytes of LDS (max 160 KB: 13631 ids)", what, num_ids, lds);
+    static bool reserved = false;
+    const int rc = reserve_lds(what, reinterpret_cast<const void*>(&group_vote_kernel<MODE>), lds_max, reserved);
+    if (rc) return rc;
     hipLaunchKernelGGL((group_vote_kernel<MODE>), dim3((unsigned)G), dim3(256), lds, s, attn, cs, ids, T, S, seg, num_ids,
                        half_mode, out_id, out_w);
     TAL_CHECK_LAUNCH(what);
@@ -211,8 +228,12 @@ extern "C" int tal_attn_pool_fwd(const float* attn, const int64_t* chunk_start, 
 extern "C" int tal_attn_vote_fwd(const float* attn, const int64_t* chunk_start, const int32_t* ids, int64_t T, int N,
                                  int S, int32_t* out_id, float* out_weight, void* stream) {
     TAL_CHECK_ARG(attn && chunk_start && ids && out_id, "tal_attn_vote_fwd: null pointer");
-    TAL_CHECK_ARG(T > 0 && N >= 0 && S > 0 && S <= 8192, "tal_attn_vote_fwd: bad shape");
+    TAL_CHECK_ARG(T > 0 && N >= 0 && S > 0, "tal_attn_vote_fwd: bad shape");
+    TAL_CHECK_ARG(S <= 8192, "tal_attn_vote_fwd: S = %d (max 8192: S * 8 bytes of LDS)", S);
     if (N == 0) return TAL_OK;
+    static bool reserved = false;     // (S = 8187 .. 8192: S * 8 bytes and the kernel's 48 static bytes pass 64 KB together)
+    const int rc = reserve_lds("tal_attn_vote_fwd", reinterpret_cast<const void*>(&attn_vote_kernel), (size_t)8192 * 8, reserved);
+    if (rc) return rc;
     hipLaunchKernelGGL(attn_vote_kernel, dim3((unsigned)N), dim3(256), (size_t)S * 8, (hipStream_t)stream, attn,
                        chunk_start, ids, T, S, out_id, out_weight);
     TAL_CHECK_LAUNCH("tal_attn_vote_fwd");

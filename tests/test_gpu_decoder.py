@@ -181,7 +181,8 @@ def test_core_rnn_golden():
 
 
 @pytest.mark.parametrize("B,In,H", [(1, 256, 512), (5, 256, 512), (16, 256, 512), (17, 256, 512), (64, 256, 512), (100, 256, 512),
-                                    (3, 512, 512), (7, 16, 32), (4, 48, 80)])
+                                    (3, 512, 512), (7, 16, 32), (4, 48, 80),
+                                    (256, 16, 32), (257, 16, 32)])      # the last B of the one-launch form, the first past it
 def test_gru_cell_one_launch_against_float64_and_the_three_launch_form(B, In, H):
     """tal_gru_cell_fwd as ONE launch (gru_step_kernel: both weight matrices streamed once, gate math on the MFMA tile's registers)
     against torch.nn.GRUCell arithmetic in float64 (`tal/diarization/uisrnn/uisrnn.py:27-38`) and against the three-launch form of
