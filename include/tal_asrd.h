@@ -611,6 +611,60 @@ int64_t tal_ngram_repeat_count(const int64_t* row, int64_t len, int n);
  * (may be NULL); out_val [B, k] descending; out_idx [B, k] int64 flat index beam*V + token. */
 int tal_beam_topk(const float* logprobs, const float* row_score, const uint8_t* row_done, int B,
                   int cur_beam, int V, int k, float* out_val, int64_t* out_idx, void* stream);
+/* The same beam search with its loop state on the device (System.generate(search="device"), tal/asr/system.py:124-219):
+ * per generated token the caller runs the decoder stack and tal_lm_head_fwd as before and then two calls, tal_beam_select_fwd and
+ * tal_beam_advance_fwd (three launches together); nothing is uploaded, nothing is read back.  R = B * beam row slots.
+ * Limits (TAL_EINVAL with a message beyond them): R <= 512 (above it tal_log_softmax_rows sums a row in another order), beam <= 64,
+ * beam <= cur_beam * V, L0 + length <= 65535.
+ * The caller fills the first nine fields and a zeroed rest; tal_beam_init_fwd carves the workspace and sets the others. */
+typedef struct tal_beam_ctx {
+    int32_t B, beam, L0, length, V, num_speakers;   /* L0 = priming tokens per item, length = steps at most, num_speakers 0: no speaker head */
+    void* workspace;           /* device, tal_beam_workspace_bytes(...) bytes, 16-byte aligned */
+    size_t workspace_bytes;
+    uint32_t* done_host;       /* pinned host [2] (mapped into the device's address space as hipHostMalloc memory is) or NULL: every
+                                * tal_beam_advance_fwd leaves {slots done, number of advance calls so far} there, the way
+                                * tal_greedy_step_fwd(sync = 2) delivers its token: the host looks without waiting for the stream */
+    /* --- library-owned (tal_beam_init_fwd) --- */
+    uint32_t* done_host_dev;   /* device alias of done_host */
+    uint32_t* ctl;             /* {steps done, slots done, the step in flight is live, 0} */
+    float* scores;             /* [R] running scores */
+    uint8_t* done;             /* [R] the SLOT has finished (system.py:203-215: the flag is not re-threaded) */
+    int32_t* rec_step;         /* [R] finish records, at most one per slot: the step at which it finished (-1: none), ... */
+    float* rec_score;          /* [R] ... its score ... */
+    int64_t* rec_tokens;       /* [R, L0 + length] ... and its token row after that step's append (L0 + rec_step + 1 tokens) */
+    int64_t* tokens[2];        /* token matrix, contiguous [R, L0 + s] after s steps in tokens[s & 1]; the other one is the
+                                * re-thread's target */
+    float* sel_val;            /* [B, beam] the latest selection: values ... */
+    int64_t* sel_idx;          /* ... and flat indices beam * V + token, as tal_beam_topk returns them */
+    float* part_val;           /* partial candidates of the selection */
+    int64_t* part_idx;
+    float* spk_hist;           /* [length, R, num_speakers] speaker logits as stored per step, or NULL */
+    int32_t* parent;           /* [length, R] the row each slot extended at that step, or NULL */
+    size_t state_bytes;        /* ctl ... sel_idx lie in workspace[0, state_bytes): one copy brings the whole state to the host */
+    uint32_t seq;              /* advance calls so far */
+    uint32_t _pad;
+} tal_beam_ctx;
+size_t tal_beam_workspace_bytes(int B, int beam, int L0, int length, int V, int num_speakers);   /* 0: outside the limits */
+/* generated int64 [B, L0] (device): every item's row seeds its `beam` slots (system.py:165-166); scores, flags, counters and
+ * records are zeroed.  A context may be initialised again, also with a smaller shape on the same workspace. */
+int tal_beam_init_fwd(tal_beam_ctx* c, const int64_t* generated, void* stream);
+/* Step `step` (0-based), selection: logits [B * cur_beam, V] raw last-position logits (tal_lm_head_fwd); cur_beam = 1 for step 0 on
+ * the B seed rows, else beam.  Per element (x - m) - lse in the order of tal_log_softmax_rows (<= 512 rows), + bias[row, v] for
+ * v < nl (bias [B * cur_beam, nl] contiguous or NULL with nl = 0: the LM's weighted log-probabilities, system.py:127-138), + the
+ * row's score; rows of finished slots -> -inf once cur_beam == beam; per item the top `beam` of its cur_beam x V candidates in
+ * tal_beam_topk's order.  sel_val / sel_idx are bit-identical to
+ * tal_beam_topk(tal_log_softmax_rows(logits) [+ bias], scores, done) and no [rows, V] tensor goes through memory.  The candidates
+ * of an item are spread over >= 2 workgroups per row (chunks of 2048 vocabulary entries) and merged by one workgroup per item. */
+int tal_beam_select_fwd(tal_beam_ctx* c, int step, int cur_beam, const float* logits, const float* bias, int nl, void* stream);
+/* Step `step`, bookkeeping on the latest selection: slot i of item b continues row b * beam + idx / V with token idx % V (copied into
+ * the other token buffer); new scores; spk_logits [B * cur_beam, num_speakers] (or NULL) and the parent rows are stored for the
+ * step; a slot whose token equals terminate_token (< 0: none) and that has not finished gets its finish record and its flag; the
+ * counters move on.  Once every slot has finished, later select / advance pairs change nothing (the state is the one after the
+ * step at which the reference leaves its loop, system.py:217-219), so the host may enqueue steps without waiting. */
+int tal_beam_advance_fwd(tal_beam_ctx* c, int step, int cur_beam, int64_t terminate_token, const float* spk_logits, void* stream);
+/* pairs int32 [n, 2] (device) = (slot, step): out [n, length, num_speakers] receives in out[i, 0 .. step] the speaker-logit history
+ * of the hypothesis that sat in `slot` after step `step`, read along the parent rows (pure copies; rows beyond `step` untouched). */
+int tal_beam_gather_spk_fwd(const tal_beam_ctx* c, const int32_t* pairs, int n, float* out, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Attention-weighted pooling of diarization features and speaker votes per generated token / word /

@@ -63,6 +63,15 @@ class UnalignedState(C.Structure):
                 ("num_no_improve", C.c_int32), ("window_time", C.c_int32), ("flags", C.c_int32), ("gen_pinned", C.c_int32)]
 
 
+class BeamCtx(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "beam", "L0", "length", "V", "num_speakers")] + \
+               [("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("done_host", C.c_void_p), ("done_host_dev", C.c_void_p)] + \
+               [(n, C.c_void_p) for n in ("ctl", "scores", "done", "rec_step", "rec_score", "rec_tokens")] + \
+               [("tokens", C.c_void_p * 2)] + \
+               [(n, C.c_void_p) for n in ("sel_val", "sel_idx", "part_val", "part_idx", "spk_hist", "parent")] + \
+               [("state_bytes", C.c_size_t), ("seq", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 UNALIGNED_WINDOW_MOVED, UNALIGNED_PREFIX_REWRITTEN, UNALIGNED_DONE, UNALIGNED_GROW, UNALIGNED_ALONE = 1, 2, 4, 8, 16
 
 # name -> (restype, argtypes); must list every symbol include/tal_asrd.h declares
@@ -146,6 +155,11 @@ SIGNATURES = {
     "tal_greedy_pick_fwd": (_i, [_p, _i, _p, _i, _i64, _i, _p, _p, _p]),
     "tal_log_softmax_rows": (_i, [_p, _i64, _i, _p, _p]),
     "tal_beam_topk": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "tal_beam_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "tal_beam_init_fwd": (_i, [C.POINTER(BeamCtx), _p, _p]),
+    "tal_beam_select_fwd": (_i, [C.POINTER(BeamCtx), _i, _i, _p, _p, _i, _p]),
+    "tal_beam_advance_fwd": (_i, [C.POINTER(BeamCtx), _i, _i, _i64, _p, _p]),
+    "tal_beam_gather_spk_fwd": (_i, [C.POINTER(BeamCtx), _p, _i, _p, _p]),
     "tal_attn_pool_fwd": (_i, [_p, _p, _p, _i64, _i, _i, _i, _i, _p, _p]),
     "tal_attn_vote_groups_fwd": (_i, [_p, _p, _p, _i64, _i, _p, _i, _i, _i, _p, _p, _p]),
     "tal_majority_vote_fwd": (_i, [_p, _i64, _p, _i, _i, _p, _p, _p]),

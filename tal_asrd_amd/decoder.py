@@ -325,10 +325,10 @@ def asr_decode(model, y_prev, encoder_out, causal=True, last_only=False, check_t
 
 
 @torch.no_grad()
-def asr_decode_spk(model, y_prev, encoder_out, causal=True, last_only=False):
+def asr_decode_spk(model, y_prev, encoder_out, causal=True, last_only=False, check_tokens=True):
     """ASRModel.decode_spk (models.py:249-289)."""
     h = _run_stack(model, model.spk_decoder, y_prev, encoder_out["speaker_out"],
-                   encoder_out["encoder_padding_mask"], causal)
+                   encoder_out["encoder_padding_mask"], causal, check_tokens)
     if last_only:
         h = h[:, -1].contiguous()
     a, b = model.speaker_head[0], model.speaker_head[1]

@@ -46,6 +46,89 @@ def _beam_topk(logprobs, scores, done, B, cur_beam, k):
     return vals, idx
 
 
+class _BeamSession:
+    """Device-side state of one beam search (tal_beam_ctx, include/tal_asrd.h): token matrix, scores, done flags, finish
+    records, counters and -- with a speaker head -- the per-step speaker logits with their parent rows, in one workspace
+    the library carves; the done counter also arrives in a pinned host word that `finished()` reads without waiting."""
+
+    def __init__(self, generated, beam, length, V, num_speakers=0, ws=None):
+        lib = N.lib()
+        self.lib = lib
+        self.dev = dev = generated.device
+        self.B, self.L0 = generated.shape
+        self.beam, self.length, self.V, self.ns = int(beam), int(length), int(V), int(num_speakers)
+        self.R = self.B * self.beam
+        self.ctx = c = N.BeamCtx()
+        c.B, c.beam, c.L0, c.length, c.V, c.num_speakers = self.B, self.beam, self.L0, self.length, self.V, self.ns
+        nws = lib.tal_beam_workspace_bytes(self.B, self.beam, self.L0, self.length, self.V, self.ns)
+        # (outside the limits the size is 0: tal_beam_init_fwd then says which limit)
+        # (a caller may hand in a workspace it used before, for any shape: tal_beam_init_fwd starts from scratch)
+        self.ws = ws if ws is not None and ws.numel() >= nws else torch.empty(max(int(nws), 16), dtype=torch.uint8, device=dev)
+        c.workspace, c.workspace_bytes = self.ws.data_ptr(), nws
+        self.done_host = torch.zeros(2, dtype=torch.int32).pin_memory()
+        self._done_np = self.done_host.numpy()
+        c.done_host = self.done_host.data_ptr()
+        self._ref = C.byref(c)
+        self._seed = generated            # (read by the enqueued init kernel)
+        N.check(lib.tal_beam_init_fwd(self._ref, N.ptr(generated), N.stream_handle()), "tal_beam_init_fwd")
+
+    def _view(self, ptr, nbytes, dtype):
+        off = ptr - self.ctx.workspace
+        return self.ws[off:off + nbytes].view(dtype)
+
+    def tokens(self, step):
+        """The token matrix after `step` steps, int64 [R, L0 + step]: a view of the device buffer the next step embeds."""
+        n = self.L0 + step
+        return self._view(self.ctx.tokens[step & 1], self.R * n * 8, torch.int64).view(self.R, n)
+
+    def select(self, step, cur_beam, logits, bias=None):
+        nl = 0 if bias is None else bias.shape[-1]
+        N.check(self.lib.tal_beam_select_fwd(self._ref, step, cur_beam, N.ptr(logits), N.ptr(bias), nl, N.stream_handle()),
+                "tal_beam_select_fwd")
+
+    def advance(self, step, cur_beam, terminate_token=None, spk_logits=None):
+        N.check(self.lib.tal_beam_advance_fwd(self._ref, step, cur_beam, -1 if terminate_token is None else int(terminate_token),
+                                              N.ptr(spk_logits), N.stream_handle()), "tal_beam_advance_fwd")
+
+    def selection(self):
+        c = self.ctx
+        return (self._view(c.sel_val, self.R * 4, torch.float32).view(self.B, self.beam),
+                self._view(c.sel_idx, self.R * 8, torch.int64).view(self.B, self.beam))
+
+    def finished(self):
+        """Has the device reported every slot done?  One look at the pinned word, no wait."""
+        return int(self._done_np[0]) >= self.R
+
+    def state(self):
+        """One D2H copy of the state block -> dict of numpy arrays: step, n_done, tokens [R, L0 + step], scores, done, and the
+        finish records (rec_step [R] with -1 for none, rec_score, rec_tokens [R, L0 + length])."""
+        c = self.ctx
+        host = self.ws[:c.state_bytes].cpu().numpy()
+        base = c.workspace
+        R, Lmax = self.R, self.L0 + self.length
+
+        def arr(ptr, count, dtype):
+            off = ptr - base
+            return host[off:off + count * np.dtype(dtype).itemsize].view(dtype)
+        ctl = arr(c.ctl, 4, np.uint32)
+        step = int(ctl[0])
+        n = self.L0 + step
+        return {"step": step, "n_done": int(ctl[1]),
+                "tokens": arr(c.tokens[step & 1], R * n, np.int64).reshape(R, n).copy(),
+                "scores": arr(c.scores, R, np.float32).copy(), "done": arr(c.done, R, np.uint8).astype(bool),
+                "rec_step": arr(c.rec_step, R, np.int32).copy(), "rec_score": arr(c.rec_score, R, np.float32).copy(),
+                "rec_tokens": arr(c.rec_tokens, R * Lmax, np.int64).reshape(R, Lmax).copy()}
+
+    def gather_spk(self, pairs):
+        """[(slot, step)] -> CPU tensor [len(pairs), length, num_speakers]; entry i holds its hypothesis' history in [:step + 1]."""
+        out = torch.zeros(len(pairs), self.length, self.ns, dtype=torch.float32, device=self.dev)
+        if pairs:
+            p = torch.tensor(pairs, dtype=torch.int32).view(-1, 2).to(self.dev)
+            N.check(self.lib.tal_beam_gather_spk_fwd(self._ref, N.ptr(p), len(pairs), N.ptr(out), N.stream_handle()),
+                    "tal_beam_gather_spk_fwd")
+        return out.cpu()
+
+
 class _GreedySession:
     """Device-side state of the sliding-window greedy loop for tal_greedy_step_fwd: the decoder's layer structs, the
     embedding / LM-head tensors, one workspace sized for the longest prefix, the {token, attention row} result buffer
@@ -689,16 +772,42 @@ class System:
     # ------------------------------------------------------------------ aligned: batched beam search
     @torch.no_grad()
     def generate(self, audio_x, generated, audio_lens, length, beam_size=1, terminate_token=None,
-                 force_half=True, force_output=False):
+                 force_half=True, force_output=False, search="host"):
         """system.py:68-252.  Returns (output_seq, output_spk): per batch item the best
         length-normalised finished sequence (CPU LongTensor | None) and its per-step speaker
-        logits (CPU tensor [steps, num_speakers] | None)."""
+        logits (CPU tensor [steps, num_speakers] | None).
+
+        search="host" (default): the loop's bookkeeping runs on the host, one upload of the token matrix and one read-back of the
+        selection per step.  search="device": the same loop with its state on the device (_beam_loop_device) -- same sequences, same
+        speaker logits, bit for bit; B * beam_size <= 512 rows."""
+        if search not in ("host", "device"):
+            raise ValueError("search must be 'host' or 'device', got %r" % (search,))
         model = self.model
-        use_spk = self.args.spk_weight > 0
         dev = audio_x.device
         if force_half:
             audio_x = audio_x.half()                    # system.py:91-92
         encoder_out = model.encode(audio_x, audio_lens)
+        batch_size = generated.size(0)
+        loop = self._beam_loop_device if search == "device" else self._beam_loop_host
+        gen, scores, spk_embeds, finished = loop(encoder_out, generated, dev, length, beam_size, terminate_token, force_output)
+        if terminate_token is None or force_output:
+            scores_h = scores.cpu().view(batch_size, beam_size)
+            for b in range(batch_size):
+                for j in range(beam_size):
+                    row = b * beam_size + j
+                    finished[b].append((torch.from_numpy(gen[row].copy()),
+                                        spk_embeds[row].cpu() if spk_embeds is not None else None,
+                                        scores_h[b, j].item()))
+        finished = [[(cand, spk, score / len(cand)) for cand, spk, score in batch] for batch in finished]
+        output_seq = [max(batch, key=lambda x: x[-1])[0] if len(batch) > 0 else None for batch in finished]
+        output_spk = [max(batch, key=lambda x: x[-1])[1] if len(batch) > 0 else None for batch in finished]
+        return output_seq, output_spk
+
+    def _beam_loop_host(self, encoder_out, generated, dev, length, beam_size, terminate_token, force_output):
+        """The loop of system.py:96-219 with its bookkeeping on the host -> (gen [rows, len] numpy, scores [rows] device tensor,
+        spk_embeds [rows, steps, num_speakers] device tensor | None, finished: per item [(tokens, speaker logits | None, score)])."""
+        model = self.model
+        use_spk = self.args.spk_weight > 0
         batch_size = generated.size(0)
         cur_beam = 1
         gen = generated.detach().cpu().numpy().astype(np.int64)           # [rows, len] host bookkeeping
@@ -757,18 +866,72 @@ class System:
             cur_beam = beam_size
             if done.sum() >= batch_size * beam_size:
                 break
-        if terminate_token is None or force_output:
-            scores_h = scores.cpu().view(batch_size, beam_size)
-            for b in range(batch_size):
-                for j in range(beam_size):
-                    row = b * beam_size + j
-                    finished[b].append((torch.from_numpy(gen[row].copy()),
-                                        spk_embeds[row].cpu() if spk_embeds is not None else None,
-                                        scores_h[b, j].item()))
-        finished = [[(cand, spk, score / len(cand)) for cand, spk, score in batch] for batch in finished]
-        output_seq = [max(batch, key=lambda x: x[-1])[0] if len(batch) > 0 else None for batch in finished]
-        output_spk = [max(batch, key=lambda x: x[-1])[1] if len(batch) > 0 else None for batch in finished]
-        return output_seq, output_spk
+        return gen, scores, spk_embeds, finished
+
+    def _beam_loop_device(self, encoder_out, generated, dev, length, beam_size, terminate_token, force_output):
+        """The same loop with its state on the device (_BeamSession): per step the decoder stack and the LM head as in the host loop
+        (first step on the seed rows, later steps on all rows: the kernels chosen depend on the row count), then
+        tal_beam_select_fwd + tal_beam_advance_fwd -- no token upload, no read-back, no numpy re-threading, and the speaker-logit
+        history is stored once per step instead of being re-threaded.  Steps are enqueued without waiting; once every slot has
+        finished the device leaves its state alone, and the host stops enqueueing when the pinned done counter says so.  One copy
+        at the end brings tokens, scores and finish records; the records are replayed in (step, slot) order -- the order the host
+        loop appends them in -- into the same `finished` lists, so generate()'s final bookkeeping is shared."""
+        model = self.model
+        use_spk = self.args.spk_weight > 0
+        lm_active = self.lm is not None and self.args.lm_weight > 0
+        batch_size, L0 = generated.shape
+        y = generated.detach().to(device=dev, dtype=torch.int64).contiguous()      # [rows, len]
+        finished = [[] for _ in range(batch_size)]
+        if length <= 0:
+            return y.cpu().numpy(), torch.zeros(batch_size, dtype=torch.float32), None, finished
+        cur_beam = 1
+        sess = None
+        for t in range(length):
+            # (the seed tokens are the only ones that can be out of range -- later ones are `index % V` --: checked once, where the
+            #  host loop raises)
+            logits = asr_decode(model, y, encoder_out, causal=False, last_only=True, check_tokens=(t == 0))     # [rows, V]
+            V = logits.size(-1)
+            pred_speaker = asr_decode_spk(model, y, encoder_out, causal=False, last_only=True, check_tokens=(t == 0)) if use_spk else None
+            bias = None
+            if lm_active:
+                # system.py:127-138 on the device token view; the weighted log-probabilities reach the selection as an additive block
+                lm_input = torch.clamp(y, max=len(self.tokenizer) - 1)
+                lm_logits = self.lm(lm_input, causal_mask=False)[:, -1, :]
+                lm_logprobs = log_softmax(lm_logits.float().contiguous())
+                nl = min(lm_logprobs.size(-1), V)
+                bias = (lm_logprobs[:, :nl] * self.args.lm_weight).contiguous()
+            if sess is None:
+                sess = _BeamSession(y, beam_size, length, V, pred_speaker.size(-1) if use_spk else 0)
+            sess.select(t, cur_beam, logits, bias)
+            if cur_beam != beam_size:
+                assert beam_size % cur_beam == 0
+                rep = beam_size // cur_beam
+                # the reference mutates the caller-visible dict the same way (system.py:168-171);
+                # `speaker_out` is NOT repeated there either (latent reference bug for beams + speaker head)
+                encoder_out["encoder_out"] = encoder_out["encoder_out"].repeat_interleave(rep, dim=0)
+                encoder_out["encoder_padding_mask"] = encoder_out["encoder_padding_mask"].repeat_interleave(rep, dim=0)
+            if use_spk:
+                assert L0 + t + 1 == (t + 1) + 1          # (the host loop's `gen.shape[1] == spk_embeds.size(1) + 1`)
+            sess.advance(t, cur_beam, terminate_token, pred_speaker)
+            cur_beam = beam_size
+            if sess.finished():
+                break
+            y = sess.tokens(t + 1)
+        st = sess.state()
+        steps = st["step"]
+        order = sorted((int(s), slot) for slot, s in enumerate(st["rec_step"]) if s >= 0)     # (step, slot)
+        final = terminate_token is None or force_output
+        spk_rec = spk_final = None
+        if use_spk:
+            pairs = [(slot, s) for s, slot in order] + ([(row, steps - 1) for row in range(sess.R)] if final else [])
+            hist = sess.gather_spk(pairs)
+            spk_rec = {slot: hist[i, :s + 1].clone() for i, (s, slot) in enumerate(order)}
+            spk_final = hist[len(order):, :steps].contiguous() if final else None
+        rec_scores = torch.from_numpy(st["rec_score"])
+        for s, slot in order:
+            finished[slot // beam_size].append((torch.from_numpy(st["rec_tokens"][slot, :L0 + s + 1].copy()),
+                                                spk_rec[slot] if use_spk else None, rec_scores[slot]))
+        return st["tokens"], torch.from_numpy(st["scores"]), spk_final, finished
 
     # ------------------------------------------------------------------ unaligned: sliding window greedy decode
     @torch.no_grad()
