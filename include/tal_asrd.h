@@ -71,6 +71,10 @@ const char* tal_last_error(void);
  *                         at most this many per CU (default 2; 0: never)
  *   gconv_short_below     grouped convs use 64-step tiles while the long tiles would give a CU fewer workgroups than
  *                         this (default 4; 0: always the long tiles).  Results do not depend on it.
+ *   head_topk_form        tal_spk_topk_fwd: 0 = by shape (the fused kernel for E = 128 from the row count at which it measured
+ *                         faster than the generic form), 1 = generic (dense layer into the workspace + row kernel), 2 = fused
+ *   head_topk_grid        workgroups of the fused top-k launch (0 = two per CU).  Results do not depend on it beyond the rounding
+ *                         of the log-sum-exp; tests use it to put the boundaries between workgroups inside a row block.
  * tal_set_option returns TAL_EINVAL for an unknown name; tal_option_name(i) enumerates the names (NULL past the end). */
 int tal_set_option(const char* name, int value);
 int tal_get_option(const char* name, int* value);
@@ -378,6 +382,27 @@ int tal_sd_head_split_fwd(const void* x_split, int64_t M, int C, const void* w_e
                           int32_t* ids, void* workspace, size_t workspace_bytes, void* stream);
 /* Row-wise argmax of a [M, N] fp32 matrix -> int32 ids (first maximum wins). */
 int tal_argmax_rows(const float* x, int64_t M, int N, int32_t* ids, void* stream);
+
+/* Per-row top-k speaker posteriors without the logits (csrc/head_topk.hip).  For a row r:
+ *   z[r, s] = feat[r, :] . w_logit[s, :] + b_logit[s]  (fp32),   lse[r] = log sum_s exp(z[r, s])
+ *   ids[r, 0..k)  the indices of the k largest z[r, :]: value descending, ASCENDING INDEX among equal values (k = 1: tal_argmax_rows' rule)
+ *   logp[r, j] = z[r, ids[r, j]] - lse[r];   logp + lse gives the logits back
+ * feat [M, E], w_logit [S, E], b_logit [S] or NULL (zeros); ids, logp [M, k] row-major, lse [M] (may be NULL).
+ * 1 <= k <= TAL_TOPK_MAX and k <= S, anything else is TAL_EINVAL; M == 0 is TAL_OK.
+ * A bias entry may be -inf: that column adds nothing to lse, ranks below every finite column (by ascending index among its kind) and
+ * has logp = -inf -- the posterior restricted to a candidate set.  The caller guarantees one finite column per row; NaN is unspecified.
+ * Two forms (option head_topk_form): the fused kernel (E == 128, 16-byte aligned feat / w_logit: feature strip stationary in registers,
+ * exact fp32 MFMAs, running top-k and online log-sum-exp, per-workgroup partials merged in a fixed order) and the generic one (the
+ * dense layer writes the logits of at most 64 MiB worth of rows into the workspace, a row kernel reads them; E % 4 == 0 as
+ * tal_linear_fwd).  Results are bit-identical call after call in either form.
+ * workspace: tal_spk_topk_workspace_bytes(M, S, E, k) under the options in force at the call (enough for either form); too small
+ * is TAL_ENOMEM. */
+#define TAL_TOPK_MAX 16
+size_t tal_spk_topk_workspace_bytes(int64_t M, int S, int E, int k);
+int tal_spk_topk_fwd(const float* feat, int64_t M, int E, const float* w_logit, const float* b_logit, int S, int k,
+                     int32_t* ids, float* logp, float* lse, void* workspace, size_t workspace_bytes, void* stream);
+/* The same reduction over the rows of a materialised [M, N] fp32 matrix (one wave per row): ids, logp [M, k], lse [M] or NULL. */
+int tal_topk_lse_rows(const float* x, int64_t M, int N, int k, int32_t* ids, float* logp, float* lse, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Transformer decoder: ASRModel.decode / decode_spk, tal/asr/models.py:203-289,

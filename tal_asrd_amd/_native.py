@@ -16,6 +16,7 @@ TAL_TDS_EXACT_F32 = 1
 TAL_TDS_OUT_SPLIT = 2
 TAL_GCONV_MAX_K = 63    # largest kernel size of the grouped convs (any-k kernels, csrc/gconv_general.hip)
 TAL_GROUP_MAX = 16      # sessions per merged decode step (csrc/common.h)
+TAL_TOPK_MAX = 16       # largest k of tal_spk_topk_fwd / tal_topk_lse_rows
 
 c_float_p = C.c_void_p  # device pointers travel as integers
 
@@ -132,6 +133,9 @@ SIGNATURES = {
     "tal_sd_head_fwd": (_i, [_p, _i64, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _sz, _p]),
     "tal_sd_head_split_fwd": (_i, [_p, _i64, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _sz, _p]),
     "tal_argmax_rows": (_i, [_p, _i64, _i, _p, _p]),
+    "tal_spk_topk_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "tal_spk_topk_fwd": (_i, [_p, _i64, _i, _p, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "tal_topk_lse_rows": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p]),
     "tal_embed_tokens_fwd": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _p, _p]),
     "tal_add_positional_fwd": (_i, [_p, _i, _i, _i, _p, _i, _p, _p]),
     "tal_pad4": (_i64, [_i64]),

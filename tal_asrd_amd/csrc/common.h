@@ -140,6 +140,8 @@ enum Option {
     OPT_GCONV_LONG_TT,            // long inputs, 10- / 14-channel TDSBlock convs: 0 = 256- / 128-step tiles (default), 256 / 128 = that length for both
     OPT_LOGMEL_GENERAL,           // the host mirror builds general log-mel plans (csrc/logmel_general.hip) for the default 16 kHz / 80 shape too
     OPT_GCONV_GENERAL,            // tal_tds_fwd runs every grouped conv on the any-k kernels (csrc/gconv_general.hip) at k = 21 too
+    OPT_HEAD_TOPK_FORM,           // tal_spk_topk_fwd: 0 = by shape (the fused form for E = 128 from the row count at which it measured faster), 1 = generic (dense layer + row kernel), 2 = fused (csrc/head_topk.hip)
+    OPT_HEAD_TOPK_GRID,           // workgroups of the fused top-k launch (0 = two per CU); tests use it to put run boundaries inside a row block
     OPT_COUNT
 };
 int opt(Option o);

@@ -562,6 +562,29 @@ class SDModel(_Resampled, nn.Module):
         feat, logits, ids = self.encoder.forward_then(mel, head, x_mean=mean, split_ok=self._embed_split() is not None)
         return (feat, ids, logits) if want_logits else (feat, ids)
 
+    @torch.no_grad()
+    def speaker_topk(self, x_wav, k=4, sample_rate=None):
+        """speaker_ids with the posterior kept: waveform [1, L] -> (feat [T', 128], ids [T', k] int32, logp [T', k], lse [T']) -- per
+        frame the k most likely speakers (most likely first, lower id first among equal logits), their log-probabilities under the
+        softmax over all speakers, and the log-sum-exp of the row (logp + lse are the logits).  The [T', 6008] logits never reach
+        memory (ops.spk_topk).  Input forms as speaker_ids."""
+        rs = self._resampler(sample_rate)
+        if rs is not None:
+            x_wav = rs(x_wav)
+        mel, mean = self.logmelspec.forward_unsubtracted(x_wav)
+        return self.speaker_topk_from_logmel(mel, mean, k=k)
+
+    @torch.no_grad()
+    def speaker_topk_from_logmel(self, mel, mean, k=4):
+        """The same from the log-mel before its mean subtraction and the scalar to subtract (see speaker_ids_from_logmel)."""
+        def head(enc_out, enc_split=False):
+            # (the head's C entry returns behind the embedding layer when neither logits nor ids are asked for)
+            feat, _, _ = ops.sd_head(enc_out, self.spk_embed_proj.weight, self.spk_embed_proj.bias, self.spk_logit_proj.weight,
+                                     self.spk_logit_proj.bias, want_logits=False, want_ids=False, x_split=enc_split,
+                                     w_embed_split=self._embed_split() if enc_split else None)
+            return (feat,) + ops.spk_topk(feat, self.spk_logit_proj.weight, self.spk_logit_proj.bias, k)
+        return self.encoder.forward_then(mel, head, x_mean=mean, split_ok=self._embed_split() is not None)
+
     def _embed_split(self):
         """hi / lo fp16 split of spk_embed_proj.weight (None: a weight outside the fp16 range, or a width the fp16x3 layer does not
         take -- the head then runs its fp32 embedding layer on the fp32 encoder output)."""

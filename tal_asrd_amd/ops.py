@@ -512,7 +512,9 @@ def sd_head(x, w_embed, b_embed, w_logit, b_logit, want_logits=True, want_ids=Tr
     feat = torch.empty(*x.shape[:-1], E, dtype=torch.float32, device=dev)
     logits = torch.empty(*x.shape[:-1], S, dtype=torch.float32, device=dev) if want_logits else None
     ids = torch.empty(x.shape[:-1], dtype=torch.int32, device=dev) if want_ids else None
-    nws = lib.tal_sd_head_workspace_bytes(M, S) if (want_ids and not want_logits) else 0
+    # (features alone take the workspace too: the embedding layer of a medium input is then the K-sliced launch of the ids call, so
+    #  spk_topk's features are speaker_ids' features bit for bit)
+    nws = lib.tal_sd_head_workspace_bytes(M, S) if not want_logits else 0
     ws = _ws(nws, dev)
     if x_split:
         if w_embed_split is None:
@@ -538,6 +540,52 @@ def argmax_rows(x):
     ids = torch.empty(x.shape[:-1], dtype=torch.int32, device=x.device)
     N.check(lib.tal_argmax_rows(N.ptr(x), M, Nn, N.ptr(ids), N.stream_handle()), "tal_argmax_rows")
     return ids
+
+
+def _check_k(k, n, what):
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= min(N.TAL_TOPK_MAX, n):
+        raise N.NativeError("%s: k=%r outside 1..min(%d, %d columns)" % (what, k, N.TAL_TOPK_MAX, n))
+    return int(k)
+
+
+def spk_topk(feat, w_logit, b_logit, k):
+    """feat [..., E] -> (ids [..., k] int32, logp [..., k], lse [...]) of the speaker posterior softmax(feat . w_logit^T + b_logit)
+    without the logits in memory (tal_spk_topk_fwd): the k largest per row, value descending and index ascending among equal values,
+    logp = logit - lse.  b_logit None = zeros; a -inf bias entry masks that speaker."""
+    lib = N.lib()
+    feat = _f32c(feat, "spk_topk")
+    w = _f32c(w_logit, "spk_topk(w_logit)")
+    b = None if b_logit is None else _f32c(b_logit, "spk_topk(b_logit)")
+    E, S = feat.shape[-1], w.shape[0]
+    if w.dim() != 2 or w.shape[1] != E or (b is not None and b.numel() != S):
+        raise N.NativeError("spk_topk: feat [..., %d] vs w_logit %s, b_logit %s"
+                            % (E, tuple(w.shape), None if b is None else tuple(b.shape)))
+    k = _check_k(k, S, "spk_topk")
+    M = feat.numel() // E
+    lead, dev = tuple(feat.shape[:-1]), feat.device
+    ids = torch.empty(lead + (k,), dtype=torch.int32, device=dev)
+    logp = torch.empty(lead + (k,), dtype=torch.float32, device=dev)
+    lse = torch.empty(lead, dtype=torch.float32, device=dev)
+    nws = lib.tal_spk_topk_workspace_bytes(M, S, E, k)
+    ws = _ws(nws, dev)
+    N.check(lib.tal_spk_topk_fwd(N.ptr(feat), M, E, N.ptr(w), N.ptr(b), S, k, N.ptr(ids), N.ptr(logp), N.ptr(lse), N.ptr(ws), nws,
+                                 N.stream_handle()), "tal_spk_topk_fwd")
+    return ids, logp, lse
+
+
+def topk_lse_rows(x, k):
+    """x [..., n] -> (ids [..., k] int32, logp [..., k], lse [...]): the same reduction over a materialised matrix (tal_topk_lse_rows)."""
+    lib = N.lib()
+    x = _f32c(x, "topk_lse_rows")
+    Nn = x.shape[-1]
+    k = _check_k(k, Nn, "topk_lse_rows")
+    M = x.numel() // Nn
+    lead = tuple(x.shape[:-1])
+    ids = torch.empty(lead + (k,), dtype=torch.int32, device=x.device)
+    logp = torch.empty(lead + (k,), dtype=torch.float32, device=x.device)
+    lse = torch.empty(lead, dtype=torch.float32, device=x.device)
+    N.check(lib.tal_topk_lse_rows(N.ptr(x), M, Nn, k, N.ptr(ids), N.ptr(logp), N.ptr(lse), N.stream_handle()), "tal_topk_lse_rows")
+    return ids, logp, lse
 
 
 def add_positional(x, pe):
