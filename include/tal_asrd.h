@@ -75,6 +75,11 @@ const char* tal_last_error(void);
  *                         faster than the generic form), 1 = generic (dense layer into the workspace + row kernel), 2 = fused
  *   head_topk_grid        workgroups of the fused top-k launch (0 = two per CU).  Results do not depend on it beyond the rounding
  *                         of the log-sum-exp; tests use it to put the boundaries between workgroups inside a row block.
+ *   xent_form             tal_xent_rows_fwd / tal_lm_xent_fwd: 0 = by shape (the fused kernel for E = 64 / 128 from the row count at
+ *                         which it measured faster than the generic form), 1 = generic (dense layer into the workspace + row
+ *                         kernel), 2 = fused, where the shape allows (anything else is TAL_EINVAL, not a fallback)
+ *   xent_grid             workgroups of the fused scoring launch (0 = two per CU).  Results do not depend on it beyond the rounding
+ *                         of the log-sum-exp; tests use it to put the boundaries between workgroups inside a row block.
  * tal_set_option returns TAL_EINVAL for an unknown name; tal_option_name(i) enumerates the names (NULL past the end). */
 int tal_set_option(const char* name, int value);
 int tal_get_option(const char* name, int* value);
@@ -404,6 +409,32 @@ int tal_spk_topk_fwd(const float* feat, int64_t M, int E, const float* w_logit, 
 /* The same reduction over the rows of a materialised [M, N] fp32 matrix (one wave per row): ids, logp [M, k], lse [M] or NULL. */
 int tal_topk_lse_rows(const float* x, int64_t M, int N, int k, int32_t* ids, float* logp, float* lse, void* stream);
 
+/* Teacher-forced scoring without the logits (csrc/xent.hip).  For a row r of a head z[r, s] = feat[r, :] . w[s, :] + bias[s] (fp32):
+ *   lse[r]  = log sum_s exp(z[r, s])
+ *   nll[r]  = lse[r] - z[r, target[r]]   (cross-entropy, reduction 'none'; >= 0 up to rounding: the target's logit is the value the sum saw)
+ *   top1[r] = arg-max_s z[r, s], the FIRST index among equal values (tal_argmax_rows' rule)
+ * feat [M, E] with row pitch ldf >= E (floats), w [N, E], bias [N] or NULL (zeros), target int64 [M]; nll [M], lse [M] or NULL,
+ * top1 [M] or NULL.  target[r] < 0 skips the row's loss: nll[r] = 0.0f, lse / top1 are still written.  target[r] >= N gives
+ * nll[r] = +inf.  A target is never used as an address, only compared with the column index of a logit, so no target value can cause
+ * an out-of-bounds access.  A bias entry may be -inf with tal_spk_topk_fwd's meaning: the column adds nothing to lse, a target on it
+ * gives nll = +inf.  The caller guarantees one finite column per row; NaN is unspecified.  M == 0 is TAL_OK; bad shapes and null
+ * pointers are TAL_EINVAL, a short workspace is TAL_ENOMEM.
+ * Two forms (option xent_form): the fused kernel (E == 64 or 128, ldf % 4 == 0, 16-byte aligned feat / w / workspace: feature strip
+ * stationary in registers, w through LDS in 128-column tiles, exact fp32 MFMAs, online log-sum-exp with one rescale per block, running
+ * arg-max, target gather from the same accumulators; per-workgroup partials merged by a second kernel in a fixed order) and the generic
+ * one (the dense layer writes the logits of at most 64 MiB worth of rows into the workspace, a one-wave-per-row kernel reduces them;
+ * E % 4 == 0 and ldf % 4 == 0 as tal_linear_fwd).  Results are bit-identical call after call in either form.
+ * workspace: tal_xent_rows_workspace_bytes(M, N, E) under the options in force at the call: the fused form's partials (a few dozen
+ * bytes per row) where the dispatch takes that form by shape, else the generic form's logits (<= 64 MiB).  The generic form runs with
+ * as many rows at a time as the workspace it is given holds (one row of logits, N floats, at the least: anything smaller is TAL_ENOMEM),
+ * so the figure always suffices, also where the fused form was expected by shape and the operands turn out to be off the 16-byte grid. */
+size_t tal_xent_rows_workspace_bytes(int64_t M, int N, int E);
+int tal_xent_rows_fwd(const float* feat, int64_t M, int64_t ldf, int E, const float* w, const float* bias, int N,
+                      const int64_t* target, float* nll, float* lse, int32_t* top1, void* workspace, size_t workspace_bytes,
+                      void* stream);
+/* The generic form's row kernel over a materialised [M, N] fp32 matrix (one wave per row); outputs as above. */
+int tal_xent_lse_rows(const float* x, int64_t M, int N, const int64_t* target, float* nll, float* lse, int32_t* top1, void* stream);
+
 /* ------------------------------------------------------------------ *
  * Transformer decoder: ASRModel.decode / decode_spk, tal/asr/models.py:203-289,
  * ModRZTXDecoderLayer :488-528 (+ torch.nn.MultiheadAttention), PositionalEncoding
@@ -488,6 +519,15 @@ int tal_decoder_stack_fwd(const tal_decoder_layer_w* layers, int n_layers, const
  * proj_t may be NULL when embed_size == 0 (then D == E0).  workspace: M*E0 floats. */
 int tal_lm_head_fwd(const float* h, int64_t M, int64_t ldh, int D, const float* proj_t, int E0,
                     const float* emb, int V, float* logits, void* workspace, size_t workspace_bytes,
+                    void* stream);
+/* The same head scored against targets instead of written out: h, ldh, D, proj_t (NULL: D == E0), E0, emb, V as tal_lm_head_fwd;
+ * the D -> E0 projection goes into the workspace, then tal_xent_rows_fwd on the tied embedding without a bias (target int64 [M],
+ * nll [M], lse / top1 [M] or NULL; semantics, forms and options as there: E0 = 64 takes the fused form, no projection the generic one).
+ * workspace: tal_lm_xent_workspace_bytes(M, D, E0, V) (the projected rows + tal_xent_rows_workspace_bytes(M, V, E0)); too small is
+ * TAL_ENOMEM and launches nothing. */
+size_t tal_lm_xent_workspace_bytes(int64_t M, int D, int E0, int V);
+int tal_lm_xent_fwd(const float* h, int64_t M, int64_t ldh, int D, const float* proj_t, int E0, const float* emb, int V,
+                    const int64_t* target, float* nll, float* lse, int32_t* top1, void* workspace, size_t workspace_bytes,
                     void* stream);
 /* y [C, R] = x [R, C]^T */
 int tal_transpose_fwd(const float* x, int R, int Cc, float* y, void* stream);

@@ -136,6 +136,9 @@ SIGNATURES = {
     "tal_spk_topk_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "tal_spk_topk_fwd": (_i, [_p, _i64, _i, _p, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "tal_topk_lse_rows": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p]),
+    "tal_xent_rows_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "tal_xent_rows_fwd": (_i, [_p, _i64, _i64, _i, _p, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "tal_xent_lse_rows": (_i, [_p, _i64, _i, _p, _p, _p, _p, _p]),
     "tal_embed_tokens_fwd": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _p, _p]),
     "tal_add_positional_fwd": (_i, [_p, _i, _i, _i, _p, _i, _p, _p]),
     "tal_pad4": (_i64, [_i64]),
@@ -145,6 +148,8 @@ SIGNATURES = {
                                    _p, _sz, _p]),
     "tal_decoder_stack_fwd": (_i, [_p, _i, _p, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "tal_lm_head_fwd": (_i, [_p, _i64, _i64, _i, _p, _i, _p, _i, _p, _p, _sz, _p]),
+    "tal_lm_xent_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "tal_lm_xent_fwd": (_i, [_p, _i64, _i64, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "tal_transpose_fwd": (_i, [_p, _i, _i, _p, _p]),
     "tal_greedy_step_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "tal_greedy_step_fwd": (_i, [C.POINTER(GreedyCtx), _i64, _i64, _i, _p]),

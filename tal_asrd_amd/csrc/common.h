@@ -142,6 +142,8 @@ enum Option {
     OPT_GCONV_GENERAL,            // tal_tds_fwd runs every grouped conv on the any-k kernels (csrc/gconv_general.hip) at k = 21 too
     OPT_HEAD_TOPK_FORM,           // tal_spk_topk_fwd: 0 = by shape (the fused form for E = 128 from the row count at which it measured faster), 1 = generic (dense layer + row kernel), 2 = fused (csrc/head_topk.hip)
     OPT_HEAD_TOPK_GRID,           // workgroups of the fused top-k launch (0 = two per CU); tests use it to put run boundaries inside a row block
+    OPT_XENT_FORM,                // tal_xent_rows_fwd / tal_lm_xent_fwd: 0 = by shape (the fused form for E = 64 / 128 from the row count at which it measured faster), 1 = generic (dense layer + row kernel), 2 = fused (csrc/xent.hip)
+    OPT_XENT_GRID,                // workgroups of the fused scoring launch (0 = two per CU); tests use it to put run boundaries inside a row block
     OPT_COUNT
 };
 int opt(Option o);

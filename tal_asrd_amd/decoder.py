@@ -335,6 +335,62 @@ def asr_decode_spk(model, y_prev, encoder_out, causal=True, last_only=False, che
     return ops.linear(ops.linear(h, a.weight, a.bias), b.weight, b.bias)
 
 
+def _check_targets(target, y_prev, n, what):
+    """Targets are checked on the host the way _embed(check_tokens=True) checks tokens: one past the head would score +inf
+    silently, so it raises; negative targets are the documented "skip this position"."""
+    N.require_cuda(target, what)
+    if target.dtype.is_floating_point or target.dtype == torch.bool or tuple(target.shape) != tuple(y_prev.shape):
+        raise N.NativeError("%s: targets must be integers of shape %s, got %s %s"
+                            % (what, tuple(y_prev.shape), target.dtype, tuple(target.shape)))
+    t = target.to(torch.int64).contiguous()
+    if t.numel() and int(t.max()) >= n:
+        raise ValueError("%s: target id out of range [0, %d) (negative ids skip a position)" % (what, n))
+    return t
+
+
+def lm_xent(model, h, target, want_top1=False, last_only=False):
+    """h [B,U,D], target [B,U] (or [B] with last_only) -> nll (and top1) of the tied LM head without the logits (tal_lm_xent_fwd)."""
+    lib = N.lib()
+    B, U, D = h.shape
+    emb = model.embedding.weight
+    V, E0 = emb.shape
+    if last_only:
+        src, M, ldh, lead = h[:, U - 1], B, U * D, (B,)
+    else:
+        src, M, ldh, lead = h, B * U, D, (B, U)
+    pt = _proj_t(model) if model.embed_size else None
+    nll = torch.empty(lead, dtype=torch.float32, device=h.device)
+    top1 = torch.empty(lead, dtype=torch.int32, device=h.device) if want_top1 else None
+    nws = lib.tal_lm_xent_workspace_bytes(M, D, E0, V)
+    ws = ops._ws(nws, h.device)
+    N.check(lib.tal_lm_xent_fwd(C.c_void_p(src.data_ptr()), M, ldh, D, N.ptr(pt), E0, N.ptr(emb), V, N.ptr(target), N.ptr(nll), None,
+                                N.ptr(top1), N.ptr(ws), nws, N.stream_handle()), "tal_lm_xent_fwd")
+    return nll, top1
+
+
+@torch.no_grad()
+def asr_score(model, y_prev, y_target, encoder_out, causal=True, want_top1=False):
+    """Teacher-forced token scoring: the decoder stack of asr_decode, then per position the cross-entropy of the tied LM head against
+    y_target [B, U] without the [B, U, V] logits -> nll [B, U] (and top1 [B, U] int32 with want_top1).  A negative target skips its
+    position (nll = 0); a target >= V raises ValueError."""
+    V = model.embedding.weight.shape[0]
+    t = _check_targets(y_target, y_prev, V, "asr_score(y_target)")
+    h = _run_stack(model, model.decoder, y_prev, encoder_out["encoder_out"], encoder_out["encoder_padding_mask"], causal)
+    nll, top1 = lm_xent(model, h, t, want_top1)
+    return (nll, top1) if want_top1 else nll
+
+
+@torch.no_grad()
+def asr_score_spk(model, y_prev, spk_target, encoder_out, causal=True, want_top1=False):
+    """The same for the speaker head: the spk_decoder stack of asr_decode_spk, speaker_head[0] as a dense layer, then the fused
+    E = spk_embed form against speaker_head[1] with its bias -> nll [B, U] (and top1)."""
+    a, b = model.speaker_head[0], model.speaker_head[1]
+    t = _check_targets(spk_target, y_prev, b.weight.shape[0], "asr_score_spk(spk_target)")
+    h = _run_stack(model, model.spk_decoder, y_prev, encoder_out["speaker_out"], encoder_out["encoder_padding_mask"], causal)
+    out = ops.xent_rows(ops.linear(h, a.weight, a.bias), b.weight, b.bias, t, want_top1=want_top1)
+    return out
+
+
 def log_softmax(x):
     """Row-wise log_softmax over the last dim (system.py:125,366)."""
     lib = N.lib()

@@ -24,6 +24,7 @@ containers that keep the reference's key names and default initialisation; the
 wrappers below override `forward` so that a direct call (e.g.
 `model.spk_embed_proj(x)` in tal/baseline/reconcile.py:81) also runs the HIP path.
 """
+import collections
 import math
 
 import torch
@@ -686,6 +687,9 @@ class ModRZTXDecoderLayer(nn.Module):
                                      memory_key_padding_mask)
 
 
+ScoreResult = collections.namedtuple("ScoreResult", ["lm_nll", "spk_nll", "lm_top1", "spk_top1"])
+
+
 class ASRModel(_Resampled, nn.Module):
     """Joint ASR + speaker model (tal/asr/models.py:56-295)."""
 
@@ -760,6 +764,19 @@ class ASRModel(_Resampled, nn.Module):
     def decode_spk(self, y_prev, encoder_out, causal_mask=True):
         from .decoder import asr_decode_spk
         return asr_decode_spk(self, y_prev, encoder_out, causal_mask)
+
+    def score(self, y_prev, y_target, encoder_out, spk_target=None, want_top1=False):
+        """Teacher-forced scoring without the logits (decoder.asr_score / asr_score_spk): per position the cross-entropy of the
+        LM head against y_target [B, U] and, with a speaker head and spk_target [B, U], of the speaker head against that.  Negative
+        targets skip a position (nll = 0).  -> ScoreResult(lm_nll, spk_nll | None, lm_top1 | None, spk_top1 | None)."""
+        from .decoder import asr_score, asr_score_spk
+        lm = asr_score(self, y_prev, y_target, encoder_out, want_top1=want_top1)
+        lm_nll, lm_top1 = lm if want_top1 else (lm, None)
+        spk_nll = spk_top1 = None
+        if self.use_speaker_head and spk_target is not None:
+            spk = asr_score_spk(self, y_prev, spk_target, encoder_out, want_top1=want_top1)
+            spk_nll, spk_top1 = spk if want_top1 else (spk, None)
+        return ScoreResult(lm_nll, spk_nll, lm_top1, spk_top1)
 
     def forward(self, x, y_prev, audio_lens):
         encoder_out = self.encode(x, audio_lens)

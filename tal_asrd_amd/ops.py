@@ -588,6 +588,53 @@ def topk_lse_rows(x, k):
     return ids, logp, lse
 
 
+def _targets(target, lead, what):
+    """int64 targets of the leading shape `lead`, contiguous on the device (any integer dtype is widened)."""
+    N.require_cuda(target, what)
+    if target.dtype.is_floating_point or target.dtype == torch.bool or tuple(target.shape) != tuple(lead):
+        raise N.NativeError("%s: targets must be integers of shape %s, got %s %s" % (what, tuple(lead), target.dtype, tuple(target.shape)))
+    return target.to(torch.int64).contiguous()
+
+
+def xent_rows(feat, w, bias, target, want_lse=False, want_top1=False):
+    """feat [..., E], target [...] -> nll [...] (and lse [...], top1 [...] int32 on request) of softmax(feat . w^T + bias) without
+    the logits in memory (tal_xent_rows_fwd): nll = lse - logit[target]; a negative target skips the row (nll = 0), a target past the
+    head gives +inf; top1 is the arg-max with the first index among equal values.  bias None = zeros; a -inf entry masks a column."""
+    lib = N.lib()
+    feat = _f32c(feat, "xent_rows")
+    w = _f32c(w, "xent_rows(w)")
+    b = None if bias is None else _f32c(bias, "xent_rows(bias)")
+    E, S = feat.shape[-1], w.shape[0]
+    if w.dim() != 2 or w.shape[1] != E or (b is not None and b.numel() != S):
+        raise N.NativeError("xent_rows: feat [..., %d] vs w %s, bias %s" % (E, tuple(w.shape), None if b is None else tuple(b.shape)))
+    lead, dev = tuple(feat.shape[:-1]), feat.device
+    t = _targets(target, lead, "xent_rows(target)")
+    M = feat.numel() // E
+    nll = torch.empty(lead, dtype=torch.float32, device=dev)
+    lse = torch.empty(lead, dtype=torch.float32, device=dev) if want_lse else None
+    top1 = torch.empty(lead, dtype=torch.int32, device=dev) if want_top1 else None
+    nws = lib.tal_xent_rows_workspace_bytes(M, S, E)
+    ws = _ws(nws, dev)
+    N.check(lib.tal_xent_rows_fwd(N.ptr(feat), M, E, E, N.ptr(w), N.ptr(b), S, N.ptr(t), N.ptr(nll), N.ptr(lse), N.ptr(top1), N.ptr(ws),
+                                  nws, N.stream_handle()), "tal_xent_rows_fwd")
+    return (nll,) + ((lse,) if want_lse else ()) + ((top1,) if want_top1 else ()) if want_lse or want_top1 else nll
+
+
+def xent_lse_rows(x, target, want_lse=False, want_top1=False):
+    """x [..., n], target [...] -> nll (lse, top1 on request): the same reduction over a materialised matrix (tal_xent_lse_rows)."""
+    lib = N.lib()
+    x = _f32c(x, "xent_lse_rows")
+    Nn = x.shape[-1]
+    lead = tuple(x.shape[:-1])
+    t = _targets(target, lead, "xent_lse_rows(target)")
+    M = x.numel() // Nn
+    nll = torch.empty(lead, dtype=torch.float32, device=x.device)
+    lse = torch.empty(lead, dtype=torch.float32, device=x.device) if want_lse else None
+    top1 = torch.empty(lead, dtype=torch.int32, device=x.device) if want_top1 else None
+    N.check(lib.tal_xent_lse_rows(N.ptr(x), M, Nn, N.ptr(t), N.ptr(nll), N.ptr(lse), N.ptr(top1), N.stream_handle()), "tal_xent_lse_rows")
+    return (nll,) + ((lse,) if want_lse else ()) + ((top1,) if want_top1 else ()) if want_lse or want_top1 else nll
+
+
 def add_positional(x, pe):
     """x [B, U, D] + pe[:U] (PositionalEncoding.forward, tal/modules.py:63)."""
     lib = N.lib()

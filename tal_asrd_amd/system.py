@@ -17,7 +17,9 @@ KV cache would change results (hard parts).
 
 LM fusion (`self.lm`, system.py:127-138) takes any caller-side module called as lm(tokens, causal_mask=False): the
 reference's own `tal/lm` package does not exist; pinned with a stand-in LM on both sides (tests/golden/_lm_standin.py).
-Not built (not on the acoustic hot path): training / validation steps, data loaders.
+Teacher-forced scoring (`System.score`) and the reference's validation step / end (`training_step` in eval mode, system.py:529-584)
+run the decoder over all positions and score the heads against the targets without the logits (decoder.asr_score).
+Not built (not on the acoustic hot path): training (gradients, label smoothing, random token replacement), data loaders.
 The half-precision casts of the waveform (`force_half`, system.py:91-92,285) are performed as written: the model
 takes the fp16 waveform, widens it exactly in the front-end and computes in fp32 from there (BASELINE.json: logits
 within 1e-3 of the fp32 CPU path run on the same -- fp16-rounded -- audio).
@@ -768,6 +770,56 @@ class System:
             utt["utteranceTokens"] = hyp[last_split_i:split_i + 1]
             last_split_i = split_i
         return utts, generated, alignments
+
+    # ------------------------------------------------------------------ teacher-forced scoring, validation loss
+    @torch.no_grad()
+    def score(self, audio_x, audio_lens, y, y_mask, spk_ids=None):
+        """How likely is the transcript y [B, L] under the model: encode once, y_prev = y[:, :-1], y_target = y[:, 1:], per-token
+        negative log-probabilities without the logits (ASRModel.score).  Positions masked out by y_mask[:, 1:] read 0 (they go to
+        the kernel as negative targets).  -> SimpleNamespace(lm_nll [B, L-1], spk_nll [B, L-1] | None (speaker head and spk_ids),
+        lm_sum / spk_sum [B]: the per-sequence sums (minus the log-probability of each hypothesis, for rescoring), count [B])."""
+        encoder_out = self.model.encode(audio_x, audio_lens)
+        return self._score_encoded(encoder_out, y, y_mask, spk_ids)
+
+    def _score_encoded(self, encoder_out, y, y_mask, spk_ids=None):
+        keep = y_mask[:, 1:].to(device=y.device, dtype=torch.bool)
+        y_prev = y[:, :-1]
+        y_target = torch.where(keep, y[:, 1:], torch.full_like(y[:, 1:], -1))
+        spk_target = None
+        if spk_ids is not None and self.model.use_speaker_head:
+            spk_target = torch.where(keep, spk_ids[:, 1:].to(y), torch.full_like(y[:, 1:], -1))
+        r = self.model.score(y_prev, y_target, encoder_out, spk_target=spk_target)
+        return SimpleNamespace(lm_nll=r.lm_nll, spk_nll=r.spk_nll, lm_sum=r.lm_nll.sum(dim=1),
+                               spk_sum=None if r.spk_nll is None else r.spk_nll.sum(dim=1), count=keep.sum(dim=1))
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx=0):
+        """The reference's training_step in eval mode (system.py:529-576, no random token replacement, no label smoothing):
+        batch = (x, audio_lens, y, y_mask, spk_ids, ...) -> {'val_lm_loss', 'val_spk_loss', 'val_loss'} as device scalars."""
+        x, audio_lens, y, y_mask, spk_ids, *_ = batch
+        num_speakers = self.model.num_speakers
+        if num_speakers > 0 and self.args.spk_weight == 0:
+            # remove unknown speakers (system.py:533-537)
+            bound = len(self.tokenizer) + num_speakers - 1 if hasattr(self.tokenizer, "__len__") else self.model.embedding.weight.shape[0] - 1
+            y = torch.min(y, torch.tensor(bound).to(y))
+        use_spk = self.args.spk_weight > 0
+        s = self._score_encoded(self.model.encode(x, audio_lens), y, y_mask, spk_ids if use_spk else None)
+        # (the masked means are plain torch reductions: masked-out positions read 0, so the sum over all is the sum over the kept)
+        n = s.count.sum().float()
+        lm_loss = s.lm_nll.sum() / n
+        spk_loss = torch.tensor(0.).to(lm_loss)
+        if use_spk:
+            if s.spk_nll is None:
+                raise N.NativeError("validation_step: spk_weight > 0 needs a model with a speaker head")
+            spk_loss = s.spk_nll.sum() / n
+        loss = lm_loss + self.args.spk_weight * spk_loss
+        return {"val_lm_loss": lm_loss, "val_spk_loss": spk_loss, "val_loss": loss}
+
+    def validation_end(self, outputs):
+        """system.py:578-584 without the generate_single call: the mean of each metric over the steps."""
+        keys = list(outputs[0].keys())
+        metrics = {k: torch.stack([x[k] for x in outputs]).mean() for k in keys}
+        return {**metrics, "log": metrics}
 
     # ------------------------------------------------------------------ aligned: batched beam search
     @torch.no_grad()
