@@ -390,9 +390,10 @@ def test_gconv_res_matches_torch(cg, T, B):
 @pytest.mark.parametrize("cg,T,B", [(10, 700, 2), (14, 256, 1), (14, 1000, 1), (18, 300, 2), (18, 5, 1), (10, 1, 1), (18, 529, 1)])
 def test_gconv_res_f16x3_matches_float64(cg, T, B):
     """TDSBlock grouped conv on the matrix cores (fp16x3 form): same tolerance as the fp32 VALU kernel, the fused
-    hi / lo split of the output is bit-identical to tal_split_f16x3_fwd of the fp32 output, rows behind the
-    output stay untouched."""
+    hi / lo split of the output is bit-identical to tal_split_f16x3_fwd of the fp32 output, rows in front of and behind
+    the outputs stay untouched (guarded_f16x3 asserts it)."""
     from tal_asrd_amd import ops
+    from tests.test_gpu_gconv_guard import guarded_f16x3
     G = 80
     g = torch.Generator().manual_seed(1000 + cg + T)
     x = torch.randn(B, G * cg, T, generator=g) * 2.0
@@ -403,8 +404,9 @@ def test_gconv_res_f16x3_matches_float64(cg, T, B):
     wf = ops.pack_gconv_f16x3_weight(w.to(dev()), G)
     assert wf is not None
     xt = x.permute(0, 2, 1).contiguous().to(dev())
-    y, ys = ops.gconv_res_f16x3(xt, wf, b.to(dev()), 0.25, G, want_split=True)
-    y2 = ops.gconv_res_f16x3(xt, wf, b.to(dev()), 0.25, G)
+    # (both calls write into [32 rows | output | 288 rows] of 0x5A and read x from between NaN bands: the bands come back untouched)
+    y, ys = guarded_f16x3(xt, wf, b.to(dev()), G, alpha=0.25, want_split=True)
+    y2 = guarded_f16x3(xt, wf, b.to(dev()), G, alpha=0.25)
     torch.cuda.synchronize()
     np.testing.assert_allclose(y.cpu().double().numpy(), ref.permute(0, 2, 1).numpy(), atol=2e-5, rtol=1e-5)
     assert torch.equal(y, y2)
@@ -599,8 +601,9 @@ def test_linear_f16x3_short_input_kernel(M, C):
                                         (10, 14, 555, 1)])
 def test_gconv_s2_f16x3_matches_float64(cig, cog, T, B):
     """stride-2 resize conv on the matrix cores (even / odd input rows as two K segments): same tolerance as the fp32
-    VALU kernel, rows behind the output untouched."""
+    VALU kernel, rows in front of and behind the output untouched (guarded_f16x3 asserts it)."""
     from tal_asrd_amd import ops
+    from tests.test_gpu_gconv_guard import guarded_f16x3
     G = 80
     g = torch.Generator().manual_seed(cig * 100 + cog + T)
     x = torch.randn(B, G * cig, T, generator=g) * 2.0
@@ -609,7 +612,7 @@ def test_gconv_s2_f16x3_matches_float64(cig, cog, T, B):
     ref = torch.nn.functional.conv1d(x.double(), w.double(), b.double(), stride=2, groups=G).permute(0, 2, 1)
     wf = ops.pack_gconv_f16x3_weight(w.to(dev()), G, stride=2)
     assert wf is not None
-    y = ops.gconv_s2_f16x3(x.permute(0, 2, 1).contiguous().to(dev()), wf, b.to(dev()), G * cog, G)
+    y = guarded_f16x3(x.permute(0, 2, 1).contiguous().to(dev()), wf, b.to(dev()), G, c_out=G * cog)
     torch.cuda.synchronize()
     np.testing.assert_allclose(y.cpu().double().numpy(), ref.numpy(), atol=2e-5, rtol=1e-5)
 

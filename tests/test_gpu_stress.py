@@ -85,8 +85,10 @@ def test_gconv_random_shapes():
 
 def test_gconv_f16x3_random_shapes():
     """matrix-core grouped convs (TDSBlock conv with fused residual, stride-2 resize convs) on odd time axes: tile and
-    block boundaries of the 256- / 128-step tiles, inputs shorter than the halo, two batch items, guard rows."""
+    block boundaries of the 256- / 128-step tiles, inputs shorter than the halo, two batch items, guard rows (every call reads x
+    from between NaN bands and writes between bands of 0x5A, which guarded_f16x3 wants back untouched)."""
     from tal_asrd_amd import ops
+    from tests.test_gpu_gconv_guard import guarded_f16x3
     rng = np.random.default_rng(23)
     G = 80
     for _ in range(12):
@@ -99,7 +101,7 @@ def test_gconv_f16x3_random_shapes():
         b = torch.randn(G * cg, generator=g)
         ref = x.double() + 0.4 * torch.relu(torch.nn.functional.conv1d(x.double(), w.double(), b.double(), padding=10, groups=G))
         wf = ops.pack_gconv_f16x3_weight(w.to(dev()), G)
-        y = ops.gconv_res_f16x3(x.permute(0, 2, 1).contiguous().to(dev()), wf, b.to(dev()), 0.4, G)
+        y = guarded_f16x3(x.permute(0, 2, 1).contiguous().to(dev()), wf, b.to(dev()), G, alpha=0.4)
         np.testing.assert_allclose(y.cpu().double().numpy(), ref.permute(0, 2, 1).numpy(), atol=3e-5, rtol=1e-5,
                                    err_msg=str((cg, T, B)))
     for _ in range(10):
@@ -112,7 +114,7 @@ def test_gconv_f16x3_random_shapes():
         b = torch.randn(G * cog, generator=g)
         ref = torch.nn.functional.conv1d(x.double(), w.double(), b.double(), stride=2, groups=G).permute(0, 2, 1)
         wf = ops.pack_gconv_f16x3_weight(w.to(dev()), G, stride=2)
-        y = ops.gconv_s2_f16x3(x.permute(0, 2, 1).contiguous().to(dev()), wf, b.to(dev()), G * cog, G)
+        y = guarded_f16x3(x.permute(0, 2, 1).contiguous().to(dev()), wf, b.to(dev()), G, c_out=G * cog)
         np.testing.assert_allclose(y.cpu().double().numpy(), ref.numpy(), atol=3e-5, rtol=1e-5, err_msg=str((cig, cog, T, B)))
 
 
