@@ -10,6 +10,7 @@
 //   -DTOPBAR      barrier at the top of the K step (no cross-step fragment prefetch)
 //   -DPERSIST     256 workgroups walk the tiles; a tile's first operands are requested before the previous tile's epilogue
 //   -DABL=mask    1 = no operand loads in the loop, 8 = fragments from registers (timing only)
+//   -DMFMA16      the same loop on v_mfma_f32_16x16x32_f16 (4 x 10 blocks of 16 x 16 per wave) instead of 32x32x16
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -69,6 +70,180 @@ constexpr int dma_piece(int q, int slot) {
 #endif
 }
 
+#ifdef MFMA16
+// -DMFMA16: the same loop on v_mfma_f32_16x16x32_f16.  Same workgroup tile, wave tile (64 rows x 160 columns = 4 row blocks x 10
+// column blocks of 16), operand image, LDS-DMA pieces, counted vmcnt and barrier; 120 MFMAs of 16 cycles per wave and K step
+// (1,920 issue cycles as before), 8 A + 20 B fragment reads (the same 28 ds_read_b128).  One MFMA covers the whole 32-deep K
+// block: a lane's fragment is row (lane & 15), logical 16-byte slot lane >> 4 (hi halves) / 4 + (lane >> 4) (lo halves).
+// A stage is one column block: its W fragment pair serves four MFMA triples (row blocks innermost, so no two consecutive MFMAs
+// write the same accumulator).  The A fragments are in use during every stage, so the next step's are read into a second set
+// (stages 8 and 9): the loop is unrolled by six (three operand buffers x two fragment sets).
+// 80 accumulators of 4 registers: 60 through the builtin (240 AGPRs), row block 3 through inline asm in VGPRs.
+#if defined(TOPBAR) || defined(PERSIST) || (ABL & 8)
+#error "MFMA16 supports only PATTERN and ABL=1"
+#endif
+constexpr int RB = 4, CB = 10;
+__device__ __forceinline__ void mfma16_vgp(f32x4& c, const h8& a, const h8& b) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
+}
+__device__ __forceinline__ void mfma16_acc(f32x4& c, const h8& a, const h8& b) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+}
+#ifdef ASM_ACC
+#define MFMA(c, a, b, in_vgpr) do { if (in_vgpr) mfma16_vgp(c, a, b); else mfma16_acc(c, a, b); } while (0)
+#else
+#define MFMA(c, a, b, in_vgpr) do { if (in_vgpr) mfma16_vgp(c, a, b); else c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); } while (0)
+#endif
+struct Frags {
+    h8 ahi[2][RB], alo[2][RB];   // [fragment set][row block]
+    h8 bhi[5], blo[5];           // ring slot = column block % 5
+};
+
+__global__ __launch_bounds__(256, 1) void gemm_w64_kernel(const float* __restrict__ As, const float* __restrict__ Ws, float* __restrict__ C,
+                                                          int64_t M, int N, int K, int tiles_n, long long* clk, unsigned ntiles) {
+    __shared__ __attribute__((aligned(16))) float lds[NBUF * BUF_FLOATS];      // 159,744 B
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int sub = lane >> 3, srccol = ((lane & 7) ^ (((w & 1) * 4 + (lane >> 4)) & 7)) * 4;
+    auto make_rsrc = [](const float* p) {
+        const uint64_t v = reinterpret_cast<uint64_t>(p);
+        u32x4 r;
+        r[0] = __builtin_amdgcn_readfirstlane((uint32_t)v);
+        r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+        r[2] = 0x7fffffffu;
+        r[3] = 0x00020000u;
+        return r;
+    };
+    const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) float*)lds) + (unsigned)w * 1024u;
+    const unsigned tile = blockIdx.x;
+    const int64_t m0 = (int64_t)(tile / (unsigned)tiles_n) * BM;
+    const int n0 = (int)(tile % (unsigned)tiles_n) * BN;
+    const int a_rows = (int)((M - m0) < BM ? (M - m0) : BM) - 1;
+    const int b_rows = ((N - n0) < BN ? (N - n0) : BN) - 1;
+    const u32x4 rs_a = make_rsrc(As + m0 * K), rs_w = make_rsrc(Ws + (int64_t)n0 * K);
+    int voff[PER_WAVE];
+#pragma unroll
+    for (int t = 0; t < PER_WAVE; ++t) {
+        const int row = 8 * (w + 4 * t) + sub;
+        voff[t] = t < A_T ? (min(row, a_rows) * K + srccol) * 4 : (min(row - BM, b_rows) * K + srccol) * 4;
+    }
+    auto dma = [&](int t, unsigned nrec, int bufoff, int kofs) {
+        const unsigned dst = lds_base + (unsigned)(bufoff * 4 + t * 4096);
+        u32x4 rs = t < A_T ? rs_a : rs_w;
+        rs[2] = nrec;
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(dst), "v"(voff[t]), "s"(rs), "s"(kofs) : "memory");
+    };
+    f32x4 hh[RB][CB], xx[RB][CB];
+#pragma unroll
+    for (int i = 0; i < RB; ++i)
+#pragma unroll
+        for (int j = 0; j < CB; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) hh[i][j][e] = xx[i][j][e] = 0.f;
+
+    // fragment addresses: row (lane & 15) of a 16-row block; logical slot fq (hi) / 4 + fq (lo) at physical slot logical ^ fsw
+    const int frow = lane & 15, fsw = (frow >> 1) & 7, fq = lane >> 4;
+    const int a_lane = (w * 64 + frow) * 32, b_lane = (BM + frow) * 32;
+    const int sh = (fq ^ fsw) * 4, sl = ((4 + fq) ^ fsw) * 4;
+    const int nk = K / BK;
+    Frags f;
+    auto read_ahi = [&](int set, int bufoff) {
+#pragma unroll
+        for (int i = 0; i < RB; ++i) f.ahi[set][i] = *reinterpret_cast<const h8*>(lds + bufoff + a_lane + i * 16 * 32 + sh);
+    };
+    auto read_alo = [&](int set, int bufoff) {
+#pragma unroll
+        for (int i = 0; i < RB; ++i) f.alo[set][i] = *reinterpret_cast<const h8*>(lds + bufoff + a_lane + i * 16 * 32 + sl);
+    };
+    auto rb = [&](int j, int bufoff) {          // W fragments of column block j into ring slot j % 5
+        f.bhi[j % 5] = *reinterpret_cast<const h8*>(lds + bufoff + b_lane + j * 16 * 32 + sh);
+        f.blo[j % 5] = *reinterpret_cast<const h8*>(lds + bufoff + b_lane + j * 16 * 32 + sl);
+    };
+    const long long c0 = clock64(), w0 = wall_clock64();
+    constexpr unsigned NREC = 0x7fffffffu;
+#pragma unroll
+    for (int t = 0; t < PER_WAVE; ++t) dma(t, NREC, 0, 0);
+    {
+        const unsigned nrec = nk > 1 ? NREC : 0u;
+#pragma unroll
+        for (int t = 0; t < PER_WAVE; ++t) dma(t, nrec, BUF_FLOATS, BK * 4);
+    }
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_WAVE) : "memory");
+    __builtin_amdgcn_s_barrier();
+    read_ahi(0, 0);
+    rb(0, 0);
+    rb(1, 0);
+    read_alo(0, 0);
+    // one K step on the tile in buffer BUFC with fragment set SET
+    auto step = [&](auto bufc, auto setc, int kt) {
+        constexpr int cur = decltype(bufc)::value * BUF_FLOATS, nxt = ((decltype(bufc)::value + 1) % 3) * BUF_FLOATS,
+                      fil = ((decltype(bufc)::value + 2) % 3) * BUF_FLOATS, set = decltype(setc)::value;
+        const int kofs = (kt + 2) * (BK * 4);
+        const unsigned nrec = kt + 2 < nk ? NREC : 0u;
+#pragma unroll
+        for (int q = 0; q < CB; ++q) {
+            const int s = q % 5;
+            if (q == 8) {
+                // tile kt + 1 has landed (this wave's share: all but the 13 youngest loads) and is visible to all waves
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_WAVE) : "memory");
+                __builtin_amdgcn_s_barrier();
+            }
+            if (q + 2 < CB) rb(q + 2, cur);
+            else rb(q + 2 - CB, nxt);                     // stages 0 / 1 of the next step
+            if (q == 8) read_ahi(set ^ 1, nxt);
+            if (q == 9) read_alo(set ^ 1, nxt);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < RB; ++i) MFMA(hh[i][q], f.ahi[set][i], f.bhi[s], i == RB - 1);
+            if (!(ABL & 1) && dma_piece(q, 0) >= 0) { __builtin_amdgcn_sched_barrier(0); dma(dma_piece(q, 0), nrec, fil, kofs); __builtin_amdgcn_sched_barrier(0); }
+#pragma unroll
+            for (int i = 0; i < RB; ++i) MFMA(xx[i][q], f.ahi[set][i], f.blo[s], i == RB - 1);
+            if (!(ABL & 1) && dma_piece(q, 1) >= 0) { __builtin_amdgcn_sched_barrier(0); dma(dma_piece(q, 1), nrec, fil, kofs); __builtin_amdgcn_sched_barrier(0); }
+#pragma unroll
+            for (int i = 0; i < RB; ++i) MFMA(xx[i][q], f.alo[set][i], f.bhi[s], i == RB - 1);
+            if (!(ABL & 1) && dma_piece(q, 2) >= 0) { __builtin_amdgcn_sched_barrier(0); dma(dma_piece(q, 2), nrec, fil, kofs); }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    int kt = 0;
+    for (; kt + 6 <= nk; kt += 6) {
+        step(I0(), I0(), kt);
+        step(I1(), I1(), kt + 1);
+        step(I2(), I0(), kt + 2);
+        step(I0(), I1(), kt + 3);
+        step(I1(), I0(), kt + 4);
+        step(I2(), I1(), kt + 5);
+    }
+    if (kt < nk) step(I0(), I0(), kt);
+    if (kt + 1 < nk) step(I1(), I1(), kt + 1);
+    if (kt + 2 < nk) step(I2(), I0(), kt + 2);
+    if (kt + 3 < nk) step(I0(), I1(), kt + 3);
+    if (kt + 4 < nk) step(I1(), I0(), kt + 4);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");      // last MFMA results -> compiler-generated readers
+    if (clk && tid == 0 && blockIdx.x < 8192) {
+        clk[2 * blockIdx.x] = (long long)(clock64() - c0);
+        clk[2 * blockIdx.x + 1] = (long long)(wall_clock64() - w0);
+    }
+    // C layout of the 16x16 forms: column lane & 15, rows 4 (lane >> 4) + register
+    const int colb = lane & 15, rowb = 4 * (lane >> 4);
+#pragma unroll
+    for (int i = 0; i < RB; ++i)
+#pragma unroll
+        for (int j = 0; j < CB; ++j) {
+            const int col = n0 + j * 16 + colb;
+            if (col >= N) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t row = m0 + w * 64 + i * 16 + rowb + e;
+                if (row < M) C[row * N + col] = hh[i][j][e] + xx[i][j][e] * (1.0f / 2048.0f);
+            }
+        }
+}
+#else
 // The two accumulator sets of a 64 x 160 wave tile are 320 registers: more than the 256 accumulation registers, and hipcc
 // puts the accumulator of EVERY builtin MFMA of a kernel into one class (3,594 spilled registers when tried).  The MFMAs are
 // therefore inline asm: 16 accumulators live in AGPRs ("+a"), 4 in VGPRs ("+v").  An accumulate chain needs no wait states;
@@ -295,6 +470,8 @@ __global__ __launch_bounds__(256, 1) void gemm_w64_kernel(const float* __restric
   }
 #endif
 }
+
+#endif      // MFMA16
 
 static int g_lo_mask = 0;
 static void run(int64_t M, int N, int K, bool check) {

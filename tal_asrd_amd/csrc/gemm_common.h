@@ -9,11 +9,43 @@ constexpr int BK = 32;
 // ---------------------------------------------------------------------------------------------
 // shared epilogue
 // ---------------------------------------------------------------------------------------------
-template <int MODE, int NSUB>
-__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16 (&acc)[NSUB], float* lds, float* Y,
+// A wave's 32 rows x 32 NSUB columns of results, in the C/D layout of the MFMA that made them:
+//   32x32 forms (L16 = false): f32x16 [NSUB]     -- element e of block j: col 32 j + (lane & 31), row (e&3) + 8*(e>>2) + 4*(lane>>5)
+//   16x16 forms (L16 = true):  f32x4 [2][2 NSUB] -- element e of block [i][j]: col 16 j + (lane & 15), row 16 i + 4*(lane>>4) + e
+// The layout only decides how the wave's 16-row stage slice is written; everything behind the stage is the same.
+template <int NSUB, bool L16>
+struct GemmAcc { typedef f32x16 type[NSUB]; };
+template <int NSUB>
+struct GemmAcc<NSUB, true> { typedef f32x4 type[2][2 * NSUB]; };
+
+// rows 16 half .. 16 half + 15 of the wave's block -> stage[16][32 NSUB]
+template <int NSUB>
+__device__ __forceinline__ void gemm_stage_half(float* stage, const f32x16 (&acc)[NSUB], int half, int lane) {
+    constexpr int CW = 32 * NSUB;
+    const int colb = lane & 31, rowb = 4 * (lane >> 5);
+#pragma unroll
+    for (int j = 0; j < NSUB; ++j)
+#pragma unroll
+        for (int e8 = 0; e8 < 8; ++e8) {
+            const int r = rowb + (e8 & 3) + 8 * (e8 >> 2);  // 0..15 inside this half
+            stage[r * CW + j * 32 + colb] = acc[j][half * 8 + e8];
+        }
+}
+template <int NSUB>
+__device__ __forceinline__ void gemm_stage_half(float* stage, const f32x4 (&acc)[2][2 * NSUB], int half, int lane) {
+    constexpr int CW = 32 * NSUB;
+    const int colb = lane & 15, rowb = 4 * (lane >> 4);
+#pragma unroll
+    for (int j = 0; j < 2 * NSUB; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) stage[(rowb + e) * CW + j * 16 + colb] = acc[half][j][e];
+}
+
+template <int MODE, int NSUB, bool L16 = false>
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const typename GemmAcc<NSUB, L16>::type& acc, float* lds, float* Y,
                                               const float* bias, const float* res, int64_t m0, int n0, int lane,
                                               int w, int wm, int wn) {
-    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (e&3) + 8*(e>>2) + 4*(lane>>5).
+    static_assert(!(L16 && MODE == 4), "the fused arg-max reads the 32x32 layout");
     const int64_t M = g.M;
     const int N = g.N;
     const int colb = lane & 31;
@@ -22,7 +54,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16 (&
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     float amax = 0.f;              // out_split: largest |value| this lane turned into halves
     constexpr int CW = 32 * NSUB;  // columns owned by one wave
-    if (MODE == 4) {
+    if constexpr (MODE == 4) {
         // Fused arg-max over this wave's CW columns (the [M, 6008] speaker logits are never written,
         // tal/baseline/reconcile.py:84).  For a fixed accumulator element e the 32 lanes of a half
         // wave hold 32 columns of one row; columns are visited in ascending order and a strict '>'
@@ -95,14 +127,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16 (&
         __amdgpu_buffer_rsrc_t rs_bias = __builtin_amdgcn_make_buffer_rsrc(uptr(bias ? bias + n_base : Y), 0, CW * 4, 0x00020000);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-#pragma unroll
-            for (int j = 0; j < NSUB; ++j)
-#pragma unroll
-                for (int e8 = 0; e8 < 8; ++e8) {
-                    const int e = half * 8 + e8;
-                    const int r = rowb + (e8 & 3) + 8 * (e8 >> 2);  // 0..15 inside this half
-                    stage[r * CW + j * 32 + colb] = acc[j][e];
-                }
+            gemm_stage_half<NSUB>(stage, acc, half, lane);
             if (cols_full && buf_ok) {
                 // Interior fast path.  Output, residual and bias go through buffer descriptors (SGPRs) whose
                 // extent is exactly this wave's valid rows: rows past M need no clamp and no predicate (loads
@@ -214,21 +239,34 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16 (&
             }
         }
     } else {
+        auto finish_one = [&](int64_t row, int col, float bv, float a) {
+            if (row < M) {
+                float v = a + bv;
+                if (MODE == 1) v = fmaxf(v, 0.f);
+                if (MODE == 2) v = res[row * g.ldres + col] + alpha * v;
+                if (MODE == 3 && (g.scale_cols == 0 || col < g.scale_cols)) v = alpha * v;
+                Y[row * g.ldy + col] = v;
+            }
+        };
+        if constexpr (L16) {
 #pragma unroll
-        for (int j = 0; j < NSUB; ++j) {
-            const int col = n0 + (wn * NSUB + j) * 32 + colb;
-            if (col >= N) continue;
-            const float bv = bias ? bias[col] : 0.f;
+            for (int j = 0; j < 2 * NSUB; ++j) {
+                const int col = n0 + wn * CW + j * 16 + (lane & 15);
+                if (col >= N) continue;
+                const float bv = bias ? bias[col] : 0.f;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int64_t row = m0 + wm * 32 + rowb + (e & 3) + 8 * (e >> 2);
-                if (row < M) {
-                    float v = acc[j][e] + bv;
-                    if (MODE == 1) v = fmaxf(v, 0.f);
-                    if (MODE == 2) v = res[row * g.ldres + col] + alpha * v;
-                    if (MODE == 3 && (g.scale_cols == 0 || col < g.scale_cols)) v = alpha * v;
-                    Y[row * g.ldy + col] = v;
-                }
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) finish_one(m0 + wm * 32 + 16 * i + 4 * (lane >> 4) + e, col, bv, acc[i][j][e]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < NSUB; ++j) {
+                const int col = n0 + (wn * NSUB + j) * 32 + colb;
+                if (col >= N) continue;
+                const float bv = bias ? bias[col] : 0.f;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) finish_one(m0 + wm * 32 + rowb + (e & 3) + 8 * (e >> 2), col, bv, acc[j][e]);
             }
         }
     }
@@ -243,15 +281,14 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16 (&
 // group, 32-column block): lane -> row rg * 8 + lane / 8, columns b * 32 + (lane % 8) * 4, so every address is one lane
 // constant + an immediate -- no vector arithmetic left but the conversions themselves (7-8 us per round for MODE 1, the
 // same as a plain fp32 store).  Rows past M are outside the buffer descriptors (loads return 0, stores are dropped).
-template <int MODE, int NSUB>
-__device__ __forceinline__ void gemm_epilogue_split(const GemmArgs& g, const f32x16 (&acc)[NSUB], float* lds, float* Y,
+template <int MODE, int NSUB, bool L16 = false>
+__device__ __forceinline__ void gemm_epilogue_split(const GemmArgs& g, const typename GemmAcc<NSUB, L16>::type& acc, float* lds, float* Y,
                                                     const float* res, int64_t m0, int n0, int lane, int w) {
     static_assert(MODE == 1 || MODE == 2, "relu or residual");
     constexpr int CW = 32 * NSUB;
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     const int64_t M = g.M;
-    const int colb = lane & 31, rowb = 4 * (lane >> 5);
     float* stage = lds + w * (16 * CW);
     auto uptr = [](const float* p) {
         const uint64_t v = reinterpret_cast<uint64_t>(p);
@@ -285,13 +322,7 @@ __device__ __forceinline__ void gemm_epilogue_split(const GemmArgs& g, const f32
                 rl[t] = __builtin_amdgcn_raw_buffer_load_b64(rs_r, (rg ? vr1 : vr0) + b * 128 + 64, 0, 0);
             }
         }
-#pragma unroll
-        for (int j = 0; j < NSUB; ++j)
-#pragma unroll
-            for (int e8 = 0; e8 < 8; ++e8) {
-                const int r = rowb + (e8 & 3) + 8 * (e8 >> 2);
-                stage[r * CW + j * 32 + colb] = acc[j][half * 8 + e8];
-            }
+        gemm_stage_half<NSUB>(stage, acc, half, lane);
         f32x4 sv[2 * NSUB];
 #pragma unroll
         for (int t = 0; t < 2 * NSUB; ++t) sv[t] = *reinterpret_cast<const f32x4*>(sp + (t / NSUB) * 8 * CW + (t % NSUB) * 32);

@@ -11,7 +11,9 @@
 // reduced-precision trick.  Roofline: 157.3 TFLOP/s (fp32 matrix peak of MI355X; a pure-MFMA
 // loop reaches 155 on this chip, scripts/ubench/mfma_peak.hip).
 //
-// Kernels, all 4 waves x (32 rows x 32*NSUB columns) of 32x32 accumulators:
+// Kernels, all 4 waves x (32 rows x 32*NSUB columns); 32x32 accumulators, except the fp16x3 form of gemm_glds_kernel
+// (v_mfma_f32_16x16x32_f16, 2 x 2 NSUB accumulators of 16 x 16: the chip holds a higher clock on that shape,
+// profiles/dense_mfma_shape.txt):
 //   gemm_glds_kernel    128(M) x 160(N) x 32(K), the hot one (M > 512, K % 32 == 0).  Operand
 //       tiles go HBM/L2 -> LDS directly (LDS-DMA `buffer_load_dwordx4 ... lds`: SGPR descriptor,
 //       32-bit lane offset, no VGPR staging, no ds_write), double-buffered, ONE barrier per K step;
@@ -132,20 +134,31 @@ __global__ __launch_bounds__(256, F16X3 ? 2 : 1) void gemm_glds_kernel(const Gem
         }
     };
 
-    f32x16 acc[NSUB];
-    f32x16 accx[F16X3 ? NSUB : 1];     // fp16x3: the cross terms hi*lo + lo*hi (scaled by 2^11)
+    // exact fp32 form: NSUB accumulators of the 32x32 MFMA.  fp16x3 form: the wave's 32 x 32 NSUB block as 2 row blocks x
+    // 2 NSUB column blocks of v_mfma_f32_16x16x32_f16 (col = lane & 15, row = 4*(lane>>4) + e: the four elements of an
+    // accumulator belong to one column), hi*hi in acc16 and the cross terms hi*lo + lo*hi (scaled by 2^11) in accx.
+    constexpr int CB = 2 * NSUB;
+    f32x16 acc[F16X3 ? 1 : NSUB];
+    f32x4 acc16[F16X3 ? 2 : 1][F16X3 ? CB : 1], accx[F16X3 ? 2 : 1][F16X3 ? CB : 1];
+    if (F16X3) {
 #pragma unroll
-    for (int j = 0; j < NSUB; ++j) {
-        // EPI: the accumulators start from the bias (all 16 elements of acc[j] belong to column n0 + 32 j + lane % 32);
-        // a K slice starts from zero, its bias is added by the fix-up kernel
-        const float b0 = (EPI && bias && !is_slice) ? bias[n0 + j * 32 + (lane & 31)] : 0.f;
+        for (int j = 0; j < CB; ++j) {
+            // EPI: the accumulators start from the bias; a K slice starts from zero, its bias is added by the fix-up kernel
+            const float b0 = (EPI && bias && !is_slice) ? bias[n0 + j * 16 + (lane & 15)] : 0.f;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc[j][e] = b0;
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    acc16[F16X3 ? i : 0][F16X3 ? j : 0][e] = b0;
+                    accx[F16X3 ? i : 0][F16X3 ? j : 0][e] = 0.f;
+                }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < NSUB; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[F16X3 ? 0 : j][e] = 0.f;
     }
-#pragma unroll
-    for (int j = 0; j < (F16X3 ? NSUB : 1); ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) accx[j][e] = 0.f;
 
     // fragment read: row (l & 31) of a 32-row block, logical 16-byte column 2*kk + (l >> 5)
     const int frow = lane & 31;
@@ -167,36 +180,39 @@ __global__ __launch_bounds__(256, F16X3 ? 2 : 1) void gemm_glds_kernel(const Gem
         const float* As = lds + (kt & 1) * (ROWS * 32) + (wm * 32 + frow) * 32;
         const float* Bs = lds + (kt & 1) * (ROWS * 32) + (BM + frow) * 32;
         if (F16X3) {
-            // operands are hi/lo fp16 splits: a 128-byte row of this K block is [32 hi | 32 lo]; one MFMA takes 16 k,
-            // lanes < 32 the first 8 and lanes >= 32 the next 8: 16-byte slot 2g + half (hi), 4 + 2g + half (lo).
+            // operands are hi/lo fp16 splits: a 128-byte row of this K block is [32 hi | 32 lo]; one 16x16x32 MFMA takes
+            // all 32 k, lane l the 8 of group l >> 4, of row l & 15 of a 16-row block: 16-byte slot l >> 4 (hi), 4 + (l >> 4) (lo).
             // a.w = sum hi*hi + 2^-11 sum (hi*lo + lo*hi), fp32 accumulation; lo*lo (2^-22 relative) is dropped.
-            // Flattened (gk, j) stages q = NSUB gk + j: stage q issues the B fragments of stage q + 2 (and the A
-            // fragments of the next gk) before its three MFMAs -- an MFMA is only 32 cycles here, and with two
-            // waves per SIMD every LDS read needs ~200 cycles of issued matrix work between issue and use.
+            // A stage is one column block j: it issues the B fragments of stage j + 2 before its six MFMAs (the pair serves
+            // both row blocks, row blocks innermost: no two consecutive MFMAs write the same accumulator) -- an MFMA is only
+            // 16 cycles here, and with two waves per SIMD every LDS read needs ~200 cycles of issued matrix work between
+            // issue and use.  Per accumulator element and K block the order is hi*hi, hi*lo, lo*hi, as in gemm_w64.hip.
+            const int r16 = lane & 15, q16 = lane >> 4, sw16 = (r16 >> 1) & 7;
+            const int slh = (q16 ^ sw16) * 4, sll = ((4 + q16) ^ sw16) * 4;
+            const float* As16 = lds + (kt & 1) * (ROWS * 32) + (wm * 32 + r16) * 32;
+            const float* Bs16 = lds + (kt & 1) * (ROWS * 32) + (BM + r16) * 32;
             f16x8 ahi[2], alo[2], bhi[3], blo[3];
-            auto slh = [&](int gk) { return ((2 * gk + fhalf) ^ fsw) * 4; };
-            auto sll = [&](int gk) { return ((4 + 2 * gk + fhalf) ^ fsw) * 4; };
-            auto read_b = [&](int q, int slot) {
-                const int gk = q / NSUB, j = q % NSUB;
-                bhi[slot] = *reinterpret_cast<const f16x8*>(Bs + j * 32 * 32 + slh(gk));
-                blo[slot] = *reinterpret_cast<const f16x8*>(Bs + j * 32 * 32 + sll(gk));
+            auto read_b = [&](int j, int slot) {
+                bhi[slot] = *reinterpret_cast<const f16x8*>(Bs16 + j * 16 * 32 + slh);
+                blo[slot] = *reinterpret_cast<const f16x8*>(Bs16 + j * 16 * 32 + sll);
             };
-            ahi[0] = *reinterpret_cast<const f16x8*>(As + slh(0));
-            alo[0] = *reinterpret_cast<const f16x8*>(As + sll(0));
+            ahi[0] = *reinterpret_cast<const f16x8*>(As16 + slh);
+            ahi[1] = *reinterpret_cast<const f16x8*>(As16 + 16 * 32 + slh);
             read_b(0, 0);
+            alo[0] = *reinterpret_cast<const f16x8*>(As16 + sll);
+            alo[1] = *reinterpret_cast<const f16x8*>(As16 + 16 * 32 + sll);
             read_b(1, 1);
 #pragma unroll
-            for (int q = 0; q < 2 * NSUB; ++q) {
-                const int gk = q / NSUB, j = q % NSUB;
-                if (q + 2 < 2 * NSUB) read_b(q + 2, (q + 2) % 3);
-                if (q == NSUB - 2) {
-                    ahi[1] = *reinterpret_cast<const f16x8*>(As + slh(1));
-                    alo[1] = *reinterpret_cast<const f16x8*>(As + sll(1));
-                }
+            for (int j = 0; j < CB; ++j) {
+                constexpr int Z = F16X3 ? 1 : 0;      // (the exact form declares one-element arrays)
+                if (j + 2 < CB) read_b(j + 2, (j + 2) % 3);
                 __builtin_amdgcn_sched_barrier(0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi[gk], bhi[q % 3], acc[j], 0, 0, 0);
-                accx[F16X3 ? j : 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi[gk], blo[q % 3], accx[F16X3 ? j : 0], 0, 0, 0);
-                accx[F16X3 ? j : 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(alo[gk], bhi[q % 3], accx[F16X3 ? j : 0], 0, 0, 0);
+                acc16[0][Z * j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[0], bhi[j % 3], acc16[0][Z * j], 0, 0, 0);
+                acc16[Z][Z * j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[1], bhi[j % 3], acc16[Z][Z * j], 0, 0, 0);
+                accx[0][Z * j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[0], blo[j % 3], accx[0][Z * j], 0, 0, 0);
+                accx[Z][Z * j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[1], blo[j % 3], accx[Z][Z * j], 0, 0, 0);
+                accx[0][Z * j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo[0], bhi[j % 3], accx[0][Z * j], 0, 0, 0);
+                accx[Z][Z * j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo[1], bhi[j % 3], accx[Z][Z * j], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
             continue;
@@ -216,10 +232,11 @@ __global__ __launch_bounds__(256, F16X3 ? 2 : 1) void gemm_glds_kernel(const Gem
             }
 #pragma unroll
             for (int j = 0; j < NSUB; ++j) {
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].x, fb[cur][j].x, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].y, fb[cur][j].y, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].z, fb[cur][j].z, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].w, fb[cur][j].w, acc[j], 0, 0, 0);
+                constexpr int Z = F16X3 ? 0 : 1;      // (the fp16x3 form declares a one-element array)
+                acc[Z * j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].x, fb[cur][j].x, acc[Z * j], 0, 0, 0);
+                acc[Z * j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].y, fb[cur][j].y, acc[Z * j], 0, 0, 0);
+                acc[Z * j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].z, fb[cur][j].z, acc[Z * j], 0, 0, 0);
+                acc[Z * j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].w, fb[cur][j].w, acc[Z * j], 0, 0, 0);
             }
         }
     }
@@ -229,18 +246,20 @@ __global__ __launch_bounds__(256, F16X3 ? 2 : 1) void gemm_glds_kernel(const Gem
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     __builtin_amdgcn_s_setprio(3);
-    if (F16X3) {
+    if constexpr (F16X3) {
         typedef float f32x2 __attribute__((ext_vector_type(2)));
         const f32x2 s11 = {1.0f / 2048.0f, 1.0f / 2048.0f};
 #pragma unroll
-        for (int j = 0; j < NSUB; ++j)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int e = 0; e < 16; e += 2) {
-                const f32x2 x2 = {accx[F16X3 ? j : 0][e], accx[F16X3 ? j : 0][e + 1]}, a2 = {acc[j][e], acc[j][e + 1]};
-                const f32x2 o2 = __builtin_elementwise_fma(x2, s11, a2);
-                acc[j][e] = o2[0];
-                acc[j][e + 1] = o2[1];
-            }
+            for (int j = 0; j < CB; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; e += 2) {
+                    const f32x2 x2 = {accx[i][j][e], accx[i][j][e + 1]}, a2 = {acc16[i][j][e], acc16[i][j][e + 1]};
+                    const f32x2 o2 = __builtin_elementwise_fma(x2, s11, a2);
+                    acc16[i][j][e] = o2[0];
+                    acc16[i][j][e + 1] = o2[1];
+                }
     }
     if (is_slice) {
         // raw accumulators of this K slice -> scratch tile [(tile, slice)][128][BN]; the fix-up kernel
@@ -251,10 +270,13 @@ __global__ __launch_bounds__(256, F16X3 ? 2 : 1) void gemm_glds_kernel(const Gem
         gp.ldy = BN;
         gp.out_split = 0;            // partial sums stay fp32; the fix-up kernel writes the split form
         float* tile_ws = g.splitk_ws + ((size_t)(logical - g.tile_base) * g.split + slice) * (BM * BN);
-        gemm_epilogue<0, NSUB>(gp, acc, lds, tile_ws - (m0 * BN + n0), nullptr, nullptr, m0, n0, lane, w, wm, wn);
+        if constexpr (F16X3) gemm_epilogue<0, NSUB, true>(gp, acc16, lds, tile_ws - (m0 * BN + n0), nullptr, nullptr, m0, n0, lane, w, wm, wn);
+        else gemm_epilogue<0, NSUB>(gp, acc, lds, tile_ws - (m0 * BN + n0), nullptr, nullptr, m0, n0, lane, w, wm, wn);
+    } else if constexpr (F16X3) {
+        if constexpr (EPI != 0) gemm_epilogue_split<MODE, NSUB, true>(g, acc16, lds, Y, res, m0, n0, lane, w);
+        else gemm_epilogue<MODE, NSUB, true>(g, acc16, lds, Y, bias, res, m0, n0, lane, w, wm, wn);
     } else {
-        if constexpr (EPI != 0) gemm_epilogue_split<MODE, NSUB>(g, acc, lds, Y, res, m0, n0, lane, w);
-        else gemm_epilogue<MODE, NSUB>(g, acc, lds, Y, bias, res, m0, n0, lane, w, wm, wn);
+        gemm_epilogue<MODE, NSUB>(g, acc, lds, Y, bias, res, m0, n0, lane, w, wm, wn);
     }
 }
 
