@@ -80,6 +80,12 @@ const char* tal_last_error(void);
  *                         kernel), 2 = fused, where the shape allows (anything else is TAL_EINVAL, not a fallback)
  *   xent_grid             workgroups of the fused scoring launch (0 = two per CU).  Results do not depend on it beyond the rounding
  *                         of the log-sum-exp; tests use it to put the boundaries between workgroups inside a row block.
+ *   soft_embed_form       tal_soft_embed_fwd / tal_lm_soft_embed_fwd: 0 = by shape (the fused kernel for (E, D) = (64, 64) / (128, 128)
+ *                         from the row count at which it measured faster than the generic form; where no sweep showed it faster
+ *                         this means the generic form), 1 = generic (dense layer into the workspace + row kernel + dense layer),
+ *                         2 = fused, where the shape allows (anything else is TAL_EINVAL, not a fallback)
+ *   soft_embed_grid       workgroups of the fused soft-embedding launch (0 = one per CU).  Results do not depend on it beyond the
+ *                         rounding of the merge; tests use it to put the boundaries between workgroups inside a row block.
  * tal_set_option returns TAL_EINVAL for an unknown name; tal_option_name(i) enumerates the names (NULL past the end). */
 int tal_set_option(const char* name, int value);
 int tal_get_option(const char* name, int* value);
@@ -435,6 +441,34 @@ int tal_xent_rows_fwd(const float* feat, int64_t M, int64_t ldf, int E, const fl
 /* The generic form's row kernel over a materialised [M, N] fp32 matrix (one wave per row); outputs as above. */
 int tal_xent_lse_rows(const float* x, int64_t M, int N, const int64_t* target, float* nll, float* lse, int32_t* top1, void* stream);
 
+/* Softmax-weighted embeddings without the logits (csrc/soft_embed.hip).  For a row r of a head z[r, s] = feat[r, :] . w[s, :] + bias[s]:
+ *   lse[r]    = log sum_s exp(z[r, s])
+ *   out[r, :] = sum_s exp(z[r, s] - lse[r]) * values[s, :]
+ * feat [M, E] with row pitch ldf >= E (floats), w [N, E], bias [N] or NULL (zeros), values [N, D] or NULL (values = w, then D == E);
+ * out [M, D] (dense), lse [M] or NULL.  A bias entry may be -inf with tal_spk_topk_fwd's meaning: the column adds nothing to lse or
+ * out.  The caller guarantees one finite column per row; NaN is unspecified.  M == 0 is TAL_OK; bad shapes and null pointers are
+ * TAL_EINVAL, a short workspace is TAL_ENOMEM and launches nothing.
+ * Two forms (option soft_embed_form): the fused kernel ((E, D) = (64, 64) or (128, 128), ldf % 4 == 0, 16-byte aligned feat / w /
+ * values / workspace: a two-product kernel -- feature strip stationary in registers, w and values through LDS in 64-row tiles, exact
+ * fp32 MFMAs for both products, online softmax with the rescale applied once per tile to everything at the old maximum, probabilities
+ * in registers only; per-workgroup partials (max, sum, out[D]) merged by a second kernel in a fixed order) and the generic one (per
+ * chunk of at most 64 MiB of logits: the dense layer writes the logits into the workspace, a one-wave-per-row kernel turns them into
+ * probabilities in place, the dense layer multiplies them with values^T, transposed once per call into the workspace; E % 4 == 0 and
+ * ldf % 4 == 0 as tal_linear_fwd, any D >= 1).  Results are bit-identical call after call in either form.
+ * workspace: tal_soft_embed_workspace_bytes(M, N, E, D) under the options in force at the call: the fused form's partials where the
+ * dispatch takes that form by shape, else values^T + the generic form's logits (<= 64 MiB).  The generic form runs with as many rows
+ * at a time as the workspace it is given holds (values^T + one row at the least: anything smaller is TAL_ENOMEM), so the figure
+ * always suffices, also where the fused form was expected by shape and the operands turn out to be off the 16-byte grid. */
+size_t tal_soft_embed_workspace_bytes(int64_t M, int N, int E, int D);
+int tal_soft_embed_fwd(const float* feat, int64_t M, int64_t ldf, int E, const float* w, const float* bias, int N,
+                       const float* values, int D, float* out, float* lse, void* workspace, size_t workspace_bytes, void* stream);
+/* The generic form's tail over a materialised [M, N] fp32 matrix of logits x (not modified): out [M, D] = softmax(x) . values,
+ * lse [M] or NULL.  workspace: tal_soft_embed_rows_workspace_bytes(M, N, D) (values^T + the probabilities, row pitch N rounded up
+ * to a multiple of 4, of at most 64 MiB worth of rows). */
+size_t tal_soft_embed_rows_workspace_bytes(int64_t M, int N, int D);
+int tal_soft_embed_rows(const float* x, int64_t M, int N, const float* values, int D, float* out, float* lse, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ *
  * Transformer decoder: ASRModel.decode / decode_spk, tal/asr/models.py:203-289,
  * ModRZTXDecoderLayer :488-528 (+ torch.nn.MultiheadAttention), PositionalEncoding
@@ -529,6 +563,14 @@ size_t tal_lm_xent_workspace_bytes(int64_t M, int D, int E0, int V);
 int tal_lm_xent_fwd(const float* h, int64_t M, int64_t ldh, int D, const float* proj_t, int E0, const float* emb, int V,
                     const int64_t* target, float* nll, float* lse, int32_t* top1, void* workspace, size_t workspace_bytes,
                     void* stream);
+/* The tied head restricted to its columns [col_begin, V) (the speaker tokens behind the text vocabulary) and multiplied into the
+ * embeddings of those same tokens: the D -> E0 projection goes into the workspace (as tal_lm_xent_fwd), then tal_soft_embed_fwd with
+ * w = values = emb + col_begin * E0 and N = V - col_begin, no bias; out [M, E0], lse [M] or NULL.  0 <= col_begin < V.  Forms and
+ * options as tal_soft_embed_fwd (no projection, D == E0 != 64 / 128: the generic form).
+ * workspace: tal_lm_soft_embed_workspace_bytes(M, D, E0, V, col_begin); too small is TAL_ENOMEM and launches nothing. */
+size_t tal_lm_soft_embed_workspace_bytes(int64_t M, int D, int E0, int V, int col_begin);
+int tal_lm_soft_embed_fwd(const float* h, int64_t M, int64_t ldh, int D, const float* proj_t, int E0, const float* emb, int V,
+                          int col_begin, float* out, float* lse, void* workspace, size_t workspace_bytes, void* stream);
 /* y [C, R] = x [R, C]^T */
 int tal_transpose_fwd(const float* x, int R, int Cc, float* y, void* stream);
 /* Row-wise log_softmax of [M, N] (system.py:125,366), out may alias x. */

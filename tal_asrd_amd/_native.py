@@ -139,6 +139,10 @@ SIGNATURES = {
     "tal_xent_rows_workspace_bytes": (_sz, [_i64, _i, _i]),
     "tal_xent_rows_fwd": (_i, [_p, _i64, _i64, _i, _p, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "tal_xent_lse_rows": (_i, [_p, _i64, _i, _p, _p, _p, _p, _p]),
+    "tal_soft_embed_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "tal_soft_embed_fwd": (_i, [_p, _i64, _i64, _i, _p, _p, _i, _p, _i, _p, _p, _p, _sz, _p]),
+    "tal_soft_embed_rows_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "tal_soft_embed_rows": (_i, [_p, _i64, _i, _p, _i, _p, _p, _p, _sz, _p]),
     "tal_embed_tokens_fwd": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _p, _p]),
     "tal_add_positional_fwd": (_i, [_p, _i, _i, _i, _p, _i, _p, _p]),
     "tal_pad4": (_i64, [_i64]),
@@ -150,6 +154,8 @@ SIGNATURES = {
     "tal_lm_head_fwd": (_i, [_p, _i64, _i64, _i, _p, _i, _p, _i, _p, _p, _sz, _p]),
     "tal_lm_xent_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "tal_lm_xent_fwd": (_i, [_p, _i64, _i64, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "tal_lm_soft_embed_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
+    "tal_lm_soft_embed_fwd": (_i, [_p, _i64, _i64, _i, _p, _i, _p, _i, _i, _p, _p, _p, _sz, _p]),
     "tal_transpose_fwd": (_i, [_p, _i, _i, _p, _p]),
     "tal_greedy_step_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "tal_greedy_step_fwd": (_i, [C.POINTER(GreedyCtx), _i64, _i64, _i, _p]),

@@ -20,8 +20,8 @@ void set_error(const char* fmt, ...) {
 // ---- behaviour switches (tal_set_option) ---------------------------------------------------
 static const char* const g_opt_names[OPT_COUNT] = {
     "tds_exact_f32", "tds_fp32_activations", "gconv_fuse_split", "gconv_c1_generic", "head_no_astationary", "gemm_global_loads",
-    "gemm_no_splitk4", "gemm_no_glds", "gemm_no_splitk_tail", "gemm_no_w64", "logmel_no_fold", "decode_no_small", "decode_small_rows", "gemm_no_row_split", "gemm_no_n96", "gemm_s64_below", "gconv_short_below", "gconv_no_shift18", "gconv_grid_xyz", "gemm_w64_stagger", "gemm_s64_order", "decode_wide_gemm", "gemm_s64_rows", "decode_persist", "decode_persist_wgs", "logmel_mfma", "gru_unfused", "decode_no_fold", "gconv_c1_fuse", "decode_fold_rows", "gconv_long_tt", "logmel_general", "gconv_general", "head_topk_form", "head_topk_grid", "xent_form", "xent_grid"};
-static std::atomic<int> g_opt[OPT_COUNT] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {256}, {0}, {0}, {2}, {4}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {32}, {0}, {0}, {0}, {0}, {64}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
+    "gemm_no_splitk4", "gemm_no_glds", "gemm_no_splitk_tail", "gemm_no_w64", "logmel_no_fold", "decode_no_small", "decode_small_rows", "gemm_no_row_split", "gemm_no_n96", "gemm_s64_below", "gconv_short_below", "gconv_no_shift18", "gconv_grid_xyz", "gemm_w64_stagger", "gemm_s64_order", "decode_wide_gemm", "gemm_s64_rows", "decode_persist", "decode_persist_wgs", "logmel_mfma", "gru_unfused", "decode_no_fold", "gconv_c1_fuse", "decode_fold_rows", "gconv_long_tt", "logmel_general", "gconv_general", "head_topk_form", "head_topk_grid", "xent_form", "xent_grid", "soft_embed_form", "soft_embed_grid"};
+static std::atomic<int> g_opt[OPT_COUNT] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {256}, {0}, {0}, {2}, {4}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {32}, {0}, {0}, {0}, {0}, {64}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
 int opt(Option o) { return g_opt[o].load(std::memory_order_relaxed); }
 
 int device_cus() {
@@ -232,6 +232,8 @@ extern "C" int tal_set_option(const char* name, int value) {
     TAL_CHECK_ARG(i != OPT_HEAD_TOPK_GRID || value >= 0, "tal_set_option: head_topk_grid must be >= 0");
     TAL_CHECK_ARG(i != OPT_XENT_FORM || (value >= 0 && value <= 2), "tal_set_option: xent_form is 0 (auto), 1 (generic) or 2 (fused)");
     TAL_CHECK_ARG(i != OPT_XENT_GRID || value >= 0, "tal_set_option: xent_grid must be >= 0");
+    TAL_CHECK_ARG(i != OPT_SOFT_EMBED_FORM || (value >= 0 && value <= 2), "tal_set_option: soft_embed_form is 0 (auto), 1 (generic) or 2 (fused)");
+    TAL_CHECK_ARG(i != OPT_SOFT_EMBED_GRID || value >= 0, "tal_set_option: soft_embed_grid must be >= 0");
     g_opt[i].store(value, std::memory_order_relaxed);
     return TAL_OK;
 }

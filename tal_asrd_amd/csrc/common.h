@@ -144,6 +144,8 @@ enum Option {
     OPT_HEAD_TOPK_GRID,           // workgroups of the fused top-k launch (0 = two per CU); tests use it to put run boundaries inside a row block
     OPT_XENT_FORM,                // tal_xent_rows_fwd / tal_lm_xent_fwd: 0 = by shape (the fused form for E = 64 / 128 from the row count at which it measured faster), 1 = generic (dense layer + row kernel), 2 = fused (csrc/xent.hip)
     OPT_XENT_GRID,                // workgroups of the fused scoring launch (0 = two per CU); tests use it to put run boundaries inside a row block
+    OPT_SOFT_EMBED_FORM,          // tal_soft_embed_fwd / tal_lm_soft_embed_fwd: 0 = by shape (the fused form for (E, D) = (64, 64) / (128, 128) from the row count at which it measured faster), 1 = generic (dense layer + row kernel + dense layer), 2 = fused (csrc/soft_embed.hip)
+    OPT_SOFT_EMBED_GRID,          // workgroups of the fused soft-embedding launch (0 = one per CU); tests use it to put run boundaries inside a row block
     OPT_COUNT
 };
 int opt(Option o);

@@ -391,6 +391,39 @@ def asr_score_spk(model, y_prev, spk_target, encoder_out, causal=True, want_top1
     return out
 
 
+@torch.no_grad()
+def asr_speaker_token_embeds(model, y_prev, y_target, encoder_out, first_speaker_token, causal=True):
+    """The open-set speaker features of tal/asr/gen_embed.py:80-99 without the logits: the decoder stack of asr_score, the hidden rows
+    at the positions where y_target >= first_speaker_token gathered on the device, then the softmax over the speaker columns
+    [first_speaker_token, V) of the tied head multiplied into those columns' embeddings (tal_lm_soft_embed_fwd).
+    -> (positions [P, 2] int64 (batch item, position; row-major order), speaker_ids [P] int64, embeds [P, E0])."""
+    lib = N.lib()
+    if model.use_speaker_head:
+        raise N.NativeError("speaker_token_embeds: a use_speaker_head model has no speaker tokens in its vocabulary")
+    emb = model.embedding.weight
+    V, E0 = emb.shape
+    first = int(first_speaker_token)
+    if not 0 <= first < V:
+        raise N.NativeError("speaker_token_embeds: first_speaker_token=%d outside [0, %d)" % (first, V))
+    t = _check_targets(y_target, y_prev, V, "speaker_token_embeds(y_target)")
+    h = _run_stack(model, model.decoder, y_prev, encoder_out["encoder_out"], encoder_out["encoder_padding_mask"], causal)
+    D = h.shape[-1]
+    mask = t >= first
+    pos = mask.nonzero()
+    ids = t[mask] - first
+    P = pos.shape[0]
+    out = torch.empty(P, E0, dtype=torch.float32, device=h.device)
+    if P == 0:
+        return pos, ids, out
+    rows = h[pos[:, 0], pos[:, 1]].contiguous()
+    pt = _proj_t(model) if model.embed_size else None
+    nws = lib.tal_lm_soft_embed_workspace_bytes(P, D, E0, V, first)
+    ws = ops._ws(nws, h.device)
+    N.check(lib.tal_lm_soft_embed_fwd(N.ptr(rows), P, D, D, N.ptr(pt), E0, N.ptr(emb), V, first, N.ptr(out), None, N.ptr(ws), nws,
+                                      N.stream_handle()), "tal_lm_soft_embed_fwd")
+    return pos, ids, out
+
+
 def log_softmax(x):
     """Row-wise log_softmax over the last dim (system.py:125,366)."""
     lib = N.lib()

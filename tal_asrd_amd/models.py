@@ -586,6 +586,28 @@ class SDModel(_Resampled, nn.Module):
             return (feat,) + ops.spk_topk(feat, self.spk_logit_proj.weight, self.spk_logit_proj.bias, k)
         return self.encoder.forward_then(mel, head, x_mean=mean, split_ok=self._embed_split() is not None)
 
+    @torch.no_grad()
+    def speaker_soft_embeds(self, x_wav, sample_rate=None):
+        """speaker_ids with the posterior multiplied into the speaker table: waveform [1, L] -> (feat [T', 128], soft [T', 128],
+        lse [T']) with soft = softmax(spk_logit_proj(feat)) @ spk_logit_proj.weight, the per-frame analogue of the soft speaker
+        embeddings of tal/asr/gen_embed.py:96-99.  Neither the [T', 6008] logits nor the probabilities reach memory
+        (ops.soft_embed).  Input forms as speaker_ids."""
+        rs = self._resampler(sample_rate)
+        if rs is not None:
+            x_wav = rs(x_wav)
+        mel, mean = self.logmelspec.forward_unsubtracted(x_wav)
+        return self.speaker_soft_embeds_from_logmel(mel, mean)
+
+    @torch.no_grad()
+    def speaker_soft_embeds_from_logmel(self, mel, mean):
+        """The same from the log-mel before its mean subtraction and the scalar to subtract (see speaker_ids_from_logmel)."""
+        def head(enc_out, enc_split=False):
+            feat, _, _ = ops.sd_head(enc_out, self.spk_embed_proj.weight, self.spk_embed_proj.bias, self.spk_logit_proj.weight,
+                                     self.spk_logit_proj.bias, want_logits=False, want_ids=False, x_split=enc_split,
+                                     w_embed_split=self._embed_split() if enc_split else None)
+            return (feat,) + ops.soft_embed(feat, self.spk_logit_proj.weight, self.spk_logit_proj.bias, None, want_lse=True)
+        return self.encoder.forward_then(mel, head, x_mean=mean, split_ok=self._embed_split() is not None)
+
     def _embed_split(self):
         """hi / lo fp16 split of spk_embed_proj.weight (None: a weight outside the fp16 range, or a width the fp16x3 layer does not
         take -- the head then runs its fp32 embedding layer on the fp32 encoder output)."""
@@ -777,6 +799,14 @@ class ASRModel(_Resampled, nn.Module):
             spk = asr_score_spk(self, y_prev, spk_target, encoder_out, want_top1=want_top1)
             spk_nll, spk_top1 = spk if want_top1 else (spk, None)
         return ScoreResult(lm_nll, spk_nll, lm_top1, spk_top1)
+
+    def speaker_token_embeds(self, y_prev, y_target, encoder_out, first_speaker_token):
+        """Soft speaker embeddings at the positions where the transcript emits a speaker token (tal/asr/gen_embed.py:80-99), without
+        the logits (decoder.asr_speaker_token_embeds): -> (positions [P, 2] int64, speaker_ids [P] int64, embeds [P, E0]) with
+        embeds = softmax(logits[:, first_speaker_token:]) @ embedding.weight[first_speaker_token:] of the rows where
+        y_target >= first_speaker_token; speaker_ids = y_target - first_speaker_token there.  A model with a speaker head raises."""
+        from .decoder import asr_speaker_token_embeds
+        return asr_speaker_token_embeds(self, y_prev, y_target, encoder_out, first_speaker_token)
 
     def forward(self, x, y_prev, audio_lens):
         encoder_out = self.encode(x, audio_lens)

@@ -635,6 +635,52 @@ def xent_lse_rows(x, target, want_lse=False, want_top1=False):
     return (nll,) + ((lse,) if want_lse else ()) + ((top1,) if want_top1 else ()) if want_lse or want_top1 else nll
 
 
+def soft_embed(feat, w, bias, values=None, want_lse=False):
+    """feat [..., E] -> out [..., D] (and lse [...] on request): softmax(feat . w^T + bias) . values without the logits or the
+    probabilities in memory (tal_soft_embed_fwd).  values [n, D]; None: values = w (the soft embedding of a tied head, D = E).
+    bias None = zeros; a -inf entry masks a column."""
+    lib = N.lib()
+    feat = _f32c(feat, "soft_embed")
+    w = _f32c(w, "soft_embed(w)")
+    b = None if bias is None else _f32c(bias, "soft_embed(bias)")
+    v = None if values is None else _f32c(values, "soft_embed(values)")
+    E, S = feat.shape[-1], w.shape[0]
+    if w.dim() != 2 or w.shape[1] != E or (b is not None and b.numel() != S) or (v is not None and (v.dim() != 2 or v.shape[0] != S)):
+        raise N.NativeError("soft_embed: feat [..., %d] vs w %s, bias %s, values %s"
+                            % (E, tuple(w.shape), None if b is None else tuple(b.shape), None if v is None else tuple(v.shape)))
+    D = E if v is None else v.shape[1]
+    lead, dev = tuple(feat.shape[:-1]), feat.device
+    M = feat.numel() // E
+    out = torch.empty(lead + (D,), dtype=torch.float32, device=dev)
+    lse = torch.empty(lead, dtype=torch.float32, device=dev) if want_lse else None
+    nws = lib.tal_soft_embed_workspace_bytes(M, S, E, D)
+    ws = _ws(nws, dev)
+    N.check(lib.tal_soft_embed_fwd(N.ptr(feat), M, E, E, N.ptr(w), N.ptr(b), S, N.ptr(v), D, N.ptr(out), N.ptr(lse), N.ptr(ws), nws,
+                                   N.stream_handle()), "tal_soft_embed_fwd")
+    return (out, lse) if want_lse else out
+
+
+def soft_embed_rows(x, values, want_lse=False):
+    """x [..., n] (logits), values [n, D] -> out [..., D] (and lse [...]): softmax(x) . values over a materialised matrix
+    (tal_soft_embed_rows); x is not modified."""
+    lib = N.lib()
+    x = _f32c(x, "soft_embed_rows")
+    v = _f32c(values, "soft_embed_rows(values)")
+    Nn = x.shape[-1]
+    if v.dim() != 2 or v.shape[0] != Nn:
+        raise N.NativeError("soft_embed_rows: x [..., %d] vs values %s" % (Nn, tuple(v.shape)))
+    D = v.shape[1]
+    lead = tuple(x.shape[:-1])
+    M = x.numel() // Nn
+    out = torch.empty(lead + (D,), dtype=torch.float32, device=x.device)
+    lse = torch.empty(lead, dtype=torch.float32, device=x.device) if want_lse else None
+    nws = lib.tal_soft_embed_rows_workspace_bytes(M, Nn, D)
+    ws = _ws(nws, x.device)
+    N.check(lib.tal_soft_embed_rows(N.ptr(x), M, Nn, N.ptr(v), D, N.ptr(out), N.ptr(lse), N.ptr(ws), nws, N.stream_handle()),
+            "tal_soft_embed_rows")
+    return (out, lse) if want_lse else out
+
+
 def add_positional(x, pe):
     """x [B, U, D] + pe[:U] (PositionalEncoding.forward, tal/modules.py:63)."""
     lib = N.lib()

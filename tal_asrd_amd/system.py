@@ -793,6 +793,17 @@ class System:
                                spk_sum=None if r.spk_nll is None else r.spk_nll.sum(dim=1), count=keep.sum(dim=1))
 
     @torch.no_grad()
+    def speaker_token_embeds(self, audio_x, audio_lens, y, y_mask):
+        """The open-set speaker features of tal/asr/gen_embed.py:77-99 for one batch: encode once, y_prev = y[:, :-1],
+        y_target = y[:, 1:], and at every position whose target is a speaker token (>= len(tokenizer)) the softmax over the speaker
+        columns multiplied into their embeddings, without the logits (ASRModel.speaker_token_embeds).  Positions with
+        y_mask[:, 1:] off are ignored.  -> (positions [P, 2] int64, speaker_ids [P] int64, embeds [P, E0])."""
+        encoder_out = self.model.encode(audio_x, audio_lens)
+        keep = y_mask[:, 1:].to(device=y.device, dtype=torch.bool)
+        y_target = torch.where(keep, y[:, 1:], torch.full_like(y[:, 1:], -1))
+        return self.model.speaker_token_embeds(y[:, :-1], y_target, encoder_out, len(self.tokenizer))
+
+    @torch.no_grad()
     def validation_step(self, batch, batch_idx=0):
         """The reference's training_step in eval mode (system.py:529-576, no random token replacement, no label smoothing):
         batch = (x, audio_lens, y, y_mask, spk_ids, ...) -> {'val_lm_loss', 'val_spk_loss', 'val_loss'} as device scalars."""
