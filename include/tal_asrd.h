@@ -818,6 +818,54 @@ int tal_gru_cell_fwd(const float* x, const float* h, int B, int In, int H, const
                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * WER / WDER scoring: tiled edit-distance alignment (csrc/edit_align.hip) of a batch of P ragged pairs
+ * of int32 id sequences a_p [m_p], b_p [n_p] (equal words = equal ids; tal_asrd_amd/wder.py maps words to
+ * ids).  Integer arithmetic only: every output equals wder.levenshtein / wder.align_opcodes exactly.
+ *   dist:  the unit-cost Levenshtein distance D[m][n].
+ *   path:  the alignment of wder.align_opcodes.  A second table M (matched words so far) runs in the same
+ *          sweep: M[i][0] = M[0][j] = 0; with eq = (a[i-1] == b[j-1]), sm = M[i-1][j-1] + eq, im = M[i][j-1],
+ *          dm = M[i-1][j]: M[i][j] = max(sm, im, dm).  TIE RULE: the step into (i, j) is the diagonal if
+ *          sm == max, else an insert if im == max, else a delete; on the edges (i, 0) is a delete and (0, j) an
+ *          insert.  The path is read from (m, n) back to (0, 0) and returned in FORWARD order, one byte per step:
+ *          TAL_EDIT_TAG_EQUAL / _REPLACE (diagonal step, ids equal / different), _INSERT (j advances), _DELETE
+ *          (i advances).  A pair owns m + n bytes at its path offset: the steps, then TAL_EDIT_TAG_NONE up to m + n.
+ *   counts [P, Ka, Kb] int64: a_lab / b_lab hold one label per id (same offsets as a / b, 0 <= label < Ka / Kb);
+ *          counts[p][x][y] = number of equal-or-replace steps of pair p whose reference word has label x and
+ *          whose hypothesis word has label y (the matrix of wder.sequence_match; labels that never occur are zero
+ *          rows / columns).  A label outside its range is not counted.
+ *   stats [P, 4] int64: {dist, path steps, equal steps, replace steps}; the last three are 0 without a path.
+ * Calling sequence: tal_edit_align_plan (host arithmetic only) turns the host offset tables a_off / b_off [P + 1]
+ * (ascending, a_off[p + 1] - a_off[p] = m_p) into the descriptor table desc [P, 8] int64 (host memory) and returns
+ * the workspace bytes, the path bytes (sum of m + n) and the number of kernel launches of the call (the largest
+ * number of tile anti-diagonals of any pair + 1); the caller copies desc to the device and hands both copies to
+ * tal_edit_align_fwd.  path == NULL (want_path = 0 in the plan) computes stats[:, 0] only: no M table, no
+ * back-pointers, no traceback.  counts == NULL: no labels are read.
+ * Tiles are TAL_EDIT_TILE_ROWS x TAL_EDIT_TILE_COLS cells (tal_edit_align_tile reads them back), one wave per tile;
+ * launch d of a call sweeps every tile of every pair on tile anti-diagonal d; tiles depend on each other through
+ * stream order only.  Workspace per pair: boundary rows / columns of D and M, a scratch line of m + n bytes and the
+ * back-pointer table, 2 bits per cell in whole tiles (64-bit offsets); no part of it needs initialising and nothing
+ * is kept between calls.  P <= 65535 per call, a side at most 2^31 - 1 - 2 TAL_EDIT_TILE_COLS ids.
+ * A short workspace is TAL_ENOMEM, a descriptor table that does not match the plan of this want_path TAL_EINVAL;
+ * both launch nothing.  P == 0 is TAL_OK.
+ * ------------------------------------------------------------------ */
+#define TAL_EDIT_TILE_ROWS 64
+#ifndef TAL_EDIT_TILE_COLS       /* (a measurement build may pass another power of two >= 64; profiles/edit_align.txt) */
+#define TAL_EDIT_TILE_COLS 128
+#endif
+#define TAL_EDIT_TAG_EQUAL 0
+#define TAL_EDIT_TAG_REPLACE 1
+#define TAL_EDIT_TAG_INSERT 2
+#define TAL_EDIT_TAG_DELETE 3
+#define TAL_EDIT_TAG_NONE 255
+void tal_edit_align_tile(int* rows, int* cols);
+size_t tal_edit_align_workspace_bytes(int P, const int64_t* a_off, const int64_t* b_off, int want_path);
+int tal_edit_align_plan(int P, const int64_t* a_off, const int64_t* b_off, int want_path, int64_t* desc,
+                        size_t* workspace_bytes, int64_t* path_bytes, int* launches);
+int tal_edit_align_fwd(const int64_t* desc_host, const int64_t* desc_dev, int P, const int32_t* a, const int32_t* b,
+                       const int32_t* a_lab, const int32_t* b_lab, int Ka, int Kb, int64_t* stats, uint8_t* path,
+                       int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Measurement hooks (bench.py): when enabled, every launch of the hot kernels
  * is bracketed by two hipEvents on its launch stream.  class: 0 dense-layer
  * GEMM, 1 TDSBlock grouped conv, 2 stride-2 grouped conv, 3 log-mel, 4 other.

@@ -690,3 +690,166 @@ def add_positional(x, pe):
     N.check(lib.tal_add_positional_fwd(N.ptr(x), B, U, D, N.ptr(_f32c(pe, "pe")), pe.shape[0], N.ptr(out),
                                        N.stream_handle()), "tal_add_positional_fwd")
     return out
+
+
+# ------------------------------------------------------------------ WER / WDER scoring: tiled edit-distance alignment
+EDIT_TAGS = ("equal", "replace", "insert", "delete")      # TAL_EDIT_TAG_* of include/tal_asrd.h; TAL_EDIT_TAG_NONE pads a pair's m + n bytes
+EDIT_TAG_NONE = 255
+EDIT_BUDGET_FRACTION = 0.25      # of the memory this process could still get (the K | V table's rule, system._UnalignedRun._table_fits)
+EDIT_MAX_PAIRS = 65535           # pairs per tal_edit_align_fwd call
+
+
+def edit_align_tile():
+    """(rows, cols) of a tile of the edit-distance sweep (tal_edit_align_tile)."""
+    r, c = C.c_int(), C.c_int()
+    N.lib().tal_edit_align_tile(C.byref(r), C.byref(c))
+    return r.value, c.value
+
+
+class EditAlignment:
+    """Result of edit_align for P pairs, everything on the device: stats [P, 4] int64 = (distance, path steps, equal steps, replace
+    steps), dist = stats[:, 0], path (uint8, forward order; pair p owns path[path_offsets[p] : path_offsets[p + 1]] = its steps, then
+    EDIT_TAG_NONE up to m + n) or None, counts [P, Ka, Kb] int64 or None.  path_offsets is host data; launches is the number of
+    kernel launches the call made."""
+
+    def __init__(self, stats, path, path_offsets, counts, launches, workspace_bytes):
+        self.stats, self.path, self.path_offsets, self.counts = stats, path, path_offsets, counts
+        self.launches, self.workspace_bytes = launches, workspace_bytes
+
+    @property
+    def dist(self):
+        return self.stats[:, 0]
+
+    def tags(self):
+        """The paths on the host: one uint8 array of TAL_EDIT_TAG_* per pair (copies the path and the step counts)."""
+        if self.path is None:
+            raise N.NativeError("edit_align: the call was made with want_path=False")
+        steps = self.stats[:, 1].cpu().numpy()
+        flat = self.path.cpu().numpy()
+        return [flat[o:o + int(k)] for o, k in zip(self.path_offsets[:-1], steps)]
+
+
+def _edit_is_batch(x):
+    import numpy as np
+    if isinstance(x, (torch.Tensor, np.ndarray)):
+        return x.ndim > 1
+    return len(x) > 0 and isinstance(x[0], (list, tuple, torch.Tensor, np.ndarray))
+
+
+def _edit_cat(seqs, dev, what, upper=None):
+    """Ragged integer sequences (host sequences or 1-D tensors) -> one int32 device tensor + the host offset table."""
+    import numpy as np
+    lens = [int(s.numel()) if isinstance(s, torch.Tensor) else len(s) for s in seqs]
+    off = np.zeros(len(seqs) + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    if seqs and all(isinstance(s, torch.Tensor) and s.is_cuda for s in seqs):
+        for s in seqs:
+            if s.dtype.is_floating_point or s.dtype == torch.bool or s.dim() != 1:
+                raise N.NativeError("%s: expected 1-D integer tensors, got %s %s" % (what, s.dtype, tuple(s.shape)))
+        return torch.cat([s.to(device=dev, dtype=torch.int32) for s in seqs]).contiguous(), off
+    host = np.zeros(int(off[-1]), dtype=np.int64)
+    for s, o, k in zip(seqs, off[:-1], lens):
+        if k:
+            v = np.asarray(s.cpu() if isinstance(s, torch.Tensor) else s)
+            if v.ndim != 1 or v.dtype.kind not in "iu":
+                raise N.NativeError("%s: expected 1-D integer sequences, got %s %s" % (what, v.dtype, v.shape))
+            host[o:o + k] = v
+    if host.size and (host.min() < (0 if upper is not None else -2 ** 31) or host.max() >= (upper if upper is not None else 2 ** 31)):
+        raise N.NativeError("%s: values outside [%d, %d)" % (what, 0 if upper is not None else -2 ** 31, upper if upper is not None else 2 ** 31))
+    return torch.from_numpy(host.astype(np.int32)).to(dev), off
+
+
+def edit_align(a, b, a_labels=None, b_labels=None, n_labels=None, want_path=True, budget_bytes=None, device=None):
+    """Unit-cost Levenshtein distance and the alignment of wder.align_opcodes on the device (tal_edit_align_fwd) -> EditAlignment.
+    a / b: ONE pair of integer id sequences (equal words = equal ids) or two equally long lists of them; host sequences are uploaded,
+    1-D device tensors are used where they are.  a_labels / b_labels (same shapes, labels 0 <= x < n_labels) ask for counts
+    [P, Ka, Kb]; n_labels: an int, a (Ka, Kb) pair, or None = one more than the largest label (host labels only).
+    want_path=False runs the distance sweep alone (no second table, no back-pointers, no traceback).
+    A batch is cut into calls whose workspace stays within budget_bytes (default: EDIT_BUDGET_FRACTION of the memory the process can
+    still get); a single pair beyond it raises NativeError before anything is launched.  Nothing is copied back to the host."""
+    import numpy as np
+    lib = N.lib()
+    dev = torch.device(device) if device is not None else next((x.device for x in (a, b) if isinstance(x, torch.Tensor)), torch.device("cuda:0"))
+    if not _edit_is_batch(a) and not _edit_is_batch(b):
+        a, b = [a], [b]
+        a_labels = None if a_labels is None else [a_labels]
+        b_labels = None if b_labels is None else [b_labels]
+    a, b = list(a), list(b)
+    if len(a) != len(b):
+        raise N.NativeError("edit_align: %d reference sequences vs %d hypothesis sequences" % (len(a), len(b)))
+    if dev.type != "cuda":
+        raise N.NativeError("edit_align: the hot path only runs on the GPU (HIP kernels); got device %s and there is deliberately no "
+                            "CPU fallback (wder.levenshtein / wder.align_opcodes are the host routines)" % dev)
+    if (a_labels is None) != (b_labels is None):
+        raise N.NativeError("edit_align: labels are needed for both sides or for neither")
+    labels = a_labels is not None
+    if labels and not want_path:
+        raise N.NativeError("edit_align: counts need the path (want_path=True)")
+    P = len(a)
+    Ka = Kb = 0
+    if labels:
+        if isinstance(n_labels, (tuple, list)):
+            Ka, Kb = int(n_labels[0]), int(n_labels[1])
+        elif n_labels is not None:
+            Ka = Kb = int(n_labels)
+    ids_a, a_off = _edit_cat(a, dev, "edit_align(a)")
+    ids_b, b_off = _edit_cat(b, dev, "edit_align(b)")
+    lab_a = lab_b = None
+    if labels:
+        a_labels, b_labels = list(a_labels), list(b_labels)
+        if n_labels is None:
+            if any(isinstance(s, torch.Tensor) and s.is_cuda for s in a_labels + b_labels):
+                raise N.NativeError("edit_align: n_labels is needed with device labels")
+            Ka = 1 + max([int(np.max(s)) for s in a_labels if len(s)] or [0])
+            Kb = 1 + max([int(np.max(s)) for s in b_labels if len(s)] or [0])
+        if Ka <= 0 or Kb <= 0 or Ka * Kb > 1 << 24:
+            raise N.NativeError("edit_align: n_labels = (%d, %d): both must be positive and their product at most 2^24" % (Ka, Kb))
+        lab_a, la_off = _edit_cat(a_labels, dev, "edit_align(a_labels)", Ka)
+        lab_b, lb_off = _edit_cat(b_labels, dev, "edit_align(b_labels)", Kb)
+        if not np.array_equal(la_off, a_off) or not np.array_equal(lb_off, b_off):
+            raise N.NativeError("edit_align: every label sequence must be as long as its id sequence")
+    m, n = np.diff(a_off), np.diff(b_off)
+    path_off = np.zeros(P + 1, dtype=np.int64)
+    np.cumsum(m + n, out=path_off[1:])
+    # workspace of each pair (a call's workspace is the sum over its pairs), the budget, the cut into calls
+    need = []
+    for p in range(P):
+        oa, ob = np.array([0, m[p]], dtype=np.int64), np.array([0, n[p]], dtype=np.int64)
+        need.append(int(lib.tal_edit_align_workspace_bytes(1, oa.ctypes.data, ob.ctypes.data, int(want_path))))
+    if budget_bytes is None:
+        free, _ = torch.cuda.mem_get_info(dev)
+        budget_bytes = EDIT_BUDGET_FRACTION * (free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
+    for p in range(P):
+        if need[p] > budget_bytes:
+            raise N.NativeError("edit_align: pair %d (m=%d, n=%d) needs a workspace of %d bytes, the budget is %d bytes; there is no host "
+                                "fallback (backend=\"host\" of wder.py is the host route)" % (p, m[p], n[p], need[p], int(budget_bytes)))
+    calls, p0, acc = [], 0, 0
+    for p in range(P):
+        if p > p0 and (acc + need[p] > budget_bytes or p - p0 == EDIT_MAX_PAIRS):
+            calls.append((p0, p))
+            p0, acc = p, 0
+        acc += need[p]
+    if P:
+        calls.append((p0, P))
+    stats = torch.empty((P, 4), dtype=torch.int64, device=dev)
+    path = torch.empty(max(int(path_off[-1]), 1), dtype=torch.uint8, device=dev)[:int(path_off[-1])] if want_path else None
+    counts = torch.empty((P, Ka, Kb), dtype=torch.int64, device=dev) if labels else None
+    launches, ws_max = 0, 0
+    with torch.cuda.device(dev):
+        for p0, p1 in calls:
+            k = p1 - p0
+            oa, ob = np.ascontiguousarray(a_off[p0:p1 + 1]), np.ascontiguousarray(b_off[p0:p1 + 1])
+            desc = np.zeros((k, 8), dtype=np.int64)
+            nws, npath, nl = C.c_size_t(), C.c_int64(), C.c_int()
+            N.check(lib.tal_edit_align_plan(k, oa.ctypes.data, ob.ctypes.data, int(want_path), desc.ctypes.data, C.byref(nws), C.byref(npath),
+                                            C.byref(nl)), "tal_edit_align_plan")
+            desc_dev = torch.from_numpy(desc).to(dev)
+            ws = _ws(nws.value, dev)
+            N.check(lib.tal_edit_align_fwd(desc.ctypes.data, N.ptr(desc_dev), k, N.ptr(ids_a), N.ptr(ids_b), N.ptr(lab_a), N.ptr(lab_b), Ka, Kb,
+                                           C.c_void_p(stats.data_ptr() + 32 * p0),
+                                           C.c_void_p(path.data_ptr() + int(path_off[p0])) if want_path else None,
+                                           C.c_void_p(counts.data_ptr() + 8 * Ka * Kb * p0) if labels else None,
+                                           N.ptr(ws), nws.value, N.stream_handle()), "tal_edit_align_fwd")
+            launches += nl.value
+            ws_max = max(ws_max, nws.value)
+    return EditAlignment(stats, path, path_off, counts, launches, ws_max)
