@@ -221,6 +221,43 @@ void launch_gemm_w64(const GemmArgs& g, int mode, bool splitk, dim3 grid, hipStr
 bool gemm_s64_ok(const GemmArgs& g, int mode);
 void launch_gemm_s64(GemmArgs g, int mode, hipStream_t s);
 int gemm_mode4_partials(int64_t M, int N);
+// Y [M, N] (row pitch ldy) = A [M, K] (row pitch lda) . W^T + bias through launch_gemm: the logits of the streaming heads' generic forms
+inline int launch_linear_ld(const float* a, int64_t lda, const float* w, const float* bias, int64_t M, int N, int K, float* y, int64_t ldy,
+                            hipStream_t s) {
+    GemmArgs g = {};
+    g.A = a; g.W = w; g.bias = bias; g.Y = y; g.M = M; g.N = N; g.K = K;
+    g.lda = lda; g.ldw = K; g.ldy = ldy; g.ldres = ldy; g.nb2 = 1;
+    return launch_gemm(g, 0, 1, s);
+}
+
+// ---- the D -> E0 projection in front of an LM head that runs on the projected rows (tal_lm_xent_fwd, tal_lm_soft_embed_fwd) ----
+// the projected rows [M, E0] take the head of the workspace, rounded up to 16 bytes
+inline size_t lm_proj_bytes(int64_t M, int E0) { return ((size_t)M * E0 * sizeof(float) + 15) & ~(size_t)15; }
+// t = h . proj_t^T into the head of the workspace, then stage(t, the rest of the workspace, its bytes).  check(t, need) holds the
+// second stage's own refusals and gives the bytes it needs: it runs before the projection is launched -- a refused call launches nothing.
+template <class Check, class Stage>
+int lm_head_project(const char* who, const float* h, int64_t M, int64_t ldh, int D, const float* proj_t, int E0, void* workspace,
+                    size_t workspace_bytes, hipStream_t s, Check check, Stage stage) {
+    const size_t head = lm_proj_bytes(M, E0);
+    if (!workspace || workspace_bytes < head) {
+        set_error("%s: workspace %zu < %zu bytes", who, workspace ? workspace_bytes : (size_t)0, head);
+        return TAL_ENOMEM;
+    }
+    float* t = reinterpret_cast<float*>(workspace);
+    size_t need = 0;
+    int rc = check(t, need);
+    if (rc) return rc;
+    if (workspace_bytes < head + need) {
+        set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, head + need);
+        return TAL_ENOMEM;
+    }
+    GemmArgs g = {};
+    g.nb2 = 1;
+    g.A = h; g.W = proj_t; g.Y = t; g.M = M; g.N = E0; g.K = D; g.lda = ldh; g.ldw = D; g.ldy = E0;
+    rc = launch_gemm(g, 0, 1, s);
+    if (rc) return rc;
+    return stage(t, reinterpret_cast<char*>(workspace) + head, workspace_bytes - head);
+}
 
 // internal launchers shared between translation units
 int launch_linear(const float* x, const float* w, const float* b, const float* res, float alpha, int mode,

@@ -1,11 +1,11 @@
 // Softmax-weighted embeddings without the logits: per row r of a head z[r, s] = feat[r, :] . W[s, :] + b[s]
 //   lse[r] = log sum_s exp(z[r, s]),  out[r, :] = sum_s exp(z[r, s] - lse[r]) * values[s, :]      (values [N, D]; NULL: values = W)
-// The third sibling of csrc/head_topk.hip and csrc/xent.hip.  There the posterior is reduced to a few scalars per row; here it is
-// multiplied into a second matrix, so the kernel is a fused two-product (attention-shaped) one: the queries are the rows of feat,
-// the keys the rows of W, the values the rows of `values`.
+// The streaming heads of csrc/head_stream.h reduce the posterior to a few scalars per row; here it is multiplied into a second
+// matrix, so the kernel is a fused two-product (attention-shaped) one of its own: the queries are the rows of feat, the keys the
+// rows of W, the values the rows of `values`.  It shares their run partition (csrc/head_plan.h) and host helpers.
 //
 // FUSED FORM ((E, D) = (64, 64) or (128, 128)).  A workgroup is four waves, a wave owns 32 queries; its 32 x E feature strip stays
-// in registers as E / 8 MFMA-ready fragments (as in the siblings).  Keys stream through LDS in tiles of 64: the W tile, the values
+// in registers as E / 8 MFMA-ready fragments (as in csrc/head_stream.h).  Keys stream through LDS in tiles of 64: the W tile, the values
 // tile (unless values == W: then ONE image serves both products) and the tile's bias, double-buffered, one barrier per tile, staged
 // with ordinary global loads into registers issued under the MFMAs of the tile before, then LDS writes -- no LDS-DMA, nothing in
 // flight at a barrier that the compiler does not wait for by itself.  Every product is v_mfma_f32_32x32x2_f32 (exact fp32).
@@ -26,7 +26,7 @@
 //   tile in flight) + addresses ~ 240 of the 512 a wave has at one wave per SIMD; LDS 2 x (32 + 32) KiB + 512 B = 128.5 KiB of the
 //   CU's 160 (64.5 KiB with values == W), i.e. one workgroup per CU.  A 128-key tile would double both the LDS image and the
 //   registers in flight and fit neither.
-// Work is cut into equal runs of (128-row block, 64-key tile) units as in the siblings; a workgroup leaves, per row and per slot (its
+// Work is cut into equal runs of (128-row block, 64-key tile) units (csrc/head_plan.h); a workgroup leaves, per row and per slot (its
 // rank among the workgroups of that row block), (max, sum, out[D]) unnormalised; soft_embed_merge_kernel -- one wave per row --
 // rescales to the common maximum and adds in slot order: bit-identical call after call.
 //
@@ -37,6 +37,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "head_plan.h"
 
 namespace tal {
 
@@ -45,7 +46,6 @@ namespace {
 constexpr int SBM = 128, SBN = 64;
 constexpr int SP_MAX = 16;          // most workgroup slots per row
 constexpr int SHDR = 4;             // floats in front of a partial's out[D]: (max, sum, -, -) -- keeps out[] 16-byte aligned
-constexpr size_t GENERIC_WS_MAX = (size_t)64 << 20;
 
 // rows at and above which auto dispatch takes the fused form.  Rule: the smallest row count of the sweep in profiles/soft_embed.txt
 // from which the fused form measured faster than the generic one at EVERY larger row count of the sweep.  It did at every row count
@@ -59,14 +59,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int NDB> struct VFrag;
 template <> struct VFrag<4> { typedef f32x4 type; };
 template <> struct VFrag<2> { typedef f32x2 type; };
-
-// workgroup whose run [b U / G, (b + 1) U / G) contains unit u
-__host__ __device__ inline int64_t block_of(int64_t u, int64_t U, int64_t G) {
-    int64_t b = u * G / U;
-    while ((b + 1) * U / G <= u) ++b;
-    while (b * U / G > u) --b;
-    return b;
-}
 
 // E == D.  SEP: values is a matrix of its own (a second LDS image); else values == W and the W image serves both products.
 template <int E, bool SEP>
@@ -296,35 +288,15 @@ __global__ __launch_bounds__(256) void transpose_values_kernel(const float* __re
     vt[i] = s < N ? values[s * D + d] : 0.f;
 }
 
-// workgroups of the fused launch and slots per row.  A run is U / grid units or one more; a row block's NT units then meet at most
-// 1 + ceil((NT - 1) / (U / grid)) runs.  Default: one workgroup per CU (the LDS image); runs never shorter than NT / 15 tiles.
-void soft_embed_plan(int64_t M, int S, int64_t& grid, int& hp) {
-    const int64_t nt = cdiv(S, SBN), units = cdiv(M, SBM) * nt, lmin = cdiv(nt, (int64_t)(SP_MAX - 1));
-    int64_t g = opt(OPT_SOFT_EMBED_GRID) > 0 ? opt(OPT_SOFT_EMBED_GRID) : (int64_t)device_cus();
-    if (g > units) g = units;
-    if (units / g < lmin) g = units / lmin;
-    const int64_t len = units / g, slots = 1 + cdiv(nt - 1, len);
-    grid = g;
-    hp = (int)(slots < g ? slots : g);
-}
+// one workgroup per CU by default (the LDS image)
+RunPlan fused_plan(int64_t M, int S) { return head_plan(M, S, SBM, SBN, SP_MAX, 1, device_cus(), opt(OPT_SOFT_EMBED_GRID)); }
 
-size_t fused_ws_bytes(int64_t M, int S, int D) {
-    int64_t grid;
-    int hp;
-    soft_embed_plan(M, S, grid, hp);
-    return (size_t)M * hp * (size_t)(D + SHDR) * 4;
-}
+size_t fused_ws_bytes(int64_t M, int S, int D) { return (size_t)M * fused_plan(M, S).hp * (size_t)(D + SHDR) * 4; }
 
 int64_t pitch4(int N) { return ((int64_t)N + 3) / 4 * 4; }
 size_t vt_bytes(int N, int D) { return (size_t)D * (size_t)pitch4(N) * 4; }       // (a multiple of 16)
 
-int64_t generic_chunk_rows(int64_t M, int N) {
-    int64_t rows = (int64_t)(GENERIC_WS_MAX / ((size_t)pitch4(N) * 4));
-    rows = rows < 1 ? 1 : rows;
-    return rows < M ? rows : M;
-}
-
-size_t rows_ws_bytes(int64_t M, int N, int D) { return vt_bytes(N, D) + (size_t)generic_chunk_rows(M, N) * (size_t)pitch4(N) * 4; }
+size_t rows_ws_bytes(int64_t M, int N, int D) { return vt_bytes(N, D) + (size_t)generic_chunk_rows(M, pitch4(N)) * (size_t)pitch4(N) * 4; }
 size_t rows_ws_min(int N, int D) { return vt_bytes(N, D) + (size_t)pitch4(N) * 4; }      // (one row of probabilities at least)
 
 bool fused_shape(int E, int D) { return E == D && (E == 64 || E == 128); }
@@ -353,9 +325,9 @@ int launch_soft_embed_fused(const float* feat, int64_t ldf, int E, const float* 
                             float* out, float* lse, void* workspace, hipStream_t s) {
     const int NT = (int)cdiv(S, SBN);
     const int64_t U = cdiv(M, SBM) * NT;
-    int64_t grid;
-    int hp;
-    soft_embed_plan(M, S, grid, hp);
+    const RunPlan plan = fused_plan(M, S);
+    const int64_t grid = plan.grid;
+    const int hp = plan.hp;
     float* part = reinterpret_cast<float*>(workspace);
     const bool sep = values != w;
     {
@@ -423,25 +395,20 @@ int soft_embed(const char* who, const float* feat, int64_t M, int64_t ldf, int E
     float* vt = reinterpret_cast<float*>(workspace);
     float* logits = vt + vt_bytes(N, D) / 4;
     const int64_t ldp = pitch4(N);
-    int64_t chunk = generic_chunk_rows(M, N);
+    int64_t chunk = generic_chunk_rows(M, ldp);
     const int64_t fit = (int64_t)((workspace_bytes - vt_bytes(N, D)) / ((size_t)ldp * 4));
     chunk = fit < chunk ? fit : chunk;
     int rc = launch_transpose_values(values, N, D, vt, s);
     if (rc) return rc;
     for (int64_t r0 = 0; r0 < M; r0 += chunk) {
         const int64_t rows = M - r0 < chunk ? M - r0 : chunk;
-        GemmArgs g = {};
-        g.A = feat + r0 * ldf; g.W = w; g.bias = bias; g.Y = logits; g.M = rows; g.N = N; g.K = E;
-        g.lda = ldf; g.ldw = E; g.ldy = ldp; g.ldres = ldp; g.nb2 = 1;
-        rc = launch_gemm(g, 0, 1, s);
+        rc = launch_linear_ld(feat + r0 * ldf, ldf, w, bias, rows, N, E, logits, ldp, s);
         if (rc) return rc;
         rc = launch_softmax_matmul(logits, ldp, logits, rows, N, vt, D, out + r0 * D, lse ? lse + r0 : nullptr, s);
         if (rc) return rc;
     }
     return TAL_OK;
 }
-
-size_t lm_proj_bytes(int64_t M, int E0) { return ((size_t)M * E0 * sizeof(float) + 15) & ~(size_t)15; }
 
 }  // namespace
 
@@ -486,7 +453,7 @@ extern "C" int tal_soft_embed_rows(const float* x, int64_t M, int N, const float
     float* vt = reinterpret_cast<float*>(workspace);
     float* p = vt + vt_bytes(N, D) / 4;
     const int64_t ldp = pitch4(N);
-    int64_t chunk = generic_chunk_rows(M, N);
+    int64_t chunk = generic_chunk_rows(M, ldp);
     const int64_t fit = (int64_t)((workspace_bytes - vt_bytes(N, D)) / ((size_t)ldp * 4));
     chunk = fit < chunk ? fit : chunk;
     int rc = launch_transpose_values(values, N, D, vt, s);
@@ -516,28 +483,16 @@ extern "C" int tal_lm_soft_embed_fwd(const float* h, int64_t M, int64_t ldh, int
     const int N = V - col_begin;
     if (!proj_t)
         return soft_embed("tal_lm_soft_embed_fwd", h, M, ldh, D, keys, nullptr, N, keys, E0, out, lse, workspace, workspace_bytes, s);
-    const size_t head = lm_proj_bytes(M, E0);
-    if (!workspace || workspace_bytes < head) {
-        set_error("tal_lm_soft_embed_fwd: workspace %zu < %zu bytes", workspace ? workspace_bytes : (size_t)0, head);
-        return TAL_ENOMEM;
-    }
-    float* t = reinterpret_cast<float*>(workspace);
-    GemmArgs g = {};
-    g.nb2 = 1;
-    g.A = h; g.W = proj_t; g.Y = t; g.M = M; g.N = E0; g.K = D; g.lda = ldh; g.ldw = D; g.ldy = E0;
-    // (the checks of the second stage run before the projection is launched: a refused call launches nothing)
-    const int form = opt(OPT_SOFT_EMBED_FORM);
-    TAL_CHECK_ARG(form != 2 || fused_possible(t, E0, keys, keys, E0, E0),
-                  "tal_lm_soft_embed_fwd: the fused form needs E0 == 64 or 128 and 16-byte aligned operands (E0=%d)", E0);
-    TAL_CHECK_ARG(D % 4 == 0 && E0 % 4 == 0, "tal_lm_soft_embed_fwd: D and E0 must be multiples of 4");
-    const bool fused = fused_by_shape(M, E0, E0) && fused_possible(t, E0, keys, keys, E0, E0);
-    const size_t need = head + (fused ? fused_ws_bytes(M, N, E0) : rows_ws_min(N, E0));
-    if (workspace_bytes < need) {
-        set_error("tal_lm_soft_embed_fwd: workspace %zu < %zu bytes", workspace_bytes, need);
-        return TAL_ENOMEM;
-    }
-    int rc = launch_gemm(g, 0, 1, s);
-    if (rc) return rc;
-    return soft_embed("tal_lm_soft_embed_fwd", t, M, E0, E0, keys, nullptr, N, keys, E0, out, lse, reinterpret_cast<char*>(workspace) + head,
-                      workspace_bytes - head, s);
+    return lm_head_project(
+        "tal_lm_soft_embed_fwd", h, M, ldh, D, proj_t, E0, workspace, workspace_bytes, s,
+        [&](const float* t, size_t& need) -> int {
+            TAL_CHECK_ARG(opt(OPT_SOFT_EMBED_FORM) != 2 || fused_possible(t, E0, keys, keys, E0, E0),
+                          "tal_lm_soft_embed_fwd: the fused form needs E0 == 64 or 128 and 16-byte aligned operands (E0=%d)", E0);
+            TAL_CHECK_ARG(D % 4 == 0 && E0 % 4 == 0, "tal_lm_soft_embed_fwd: D and E0 must be multiples of 4");
+            need = fused_by_shape(M, E0, E0) && fused_possible(t, E0, keys, keys, E0, E0) ? fused_ws_bytes(M, N, E0) : rows_ws_min(N, E0);
+            return TAL_OK;
+        },
+        [&](const float* t, void* ws, size_t ws_bytes) {
+            return soft_embed("tal_lm_soft_embed_fwd", t, M, E0, E0, keys, nullptr, N, keys, E0, out, lse, ws, ws_bytes, s);
+        });
 }
