@@ -289,7 +289,7 @@ extern "C" int tal_linear_fwd(const float* x, const float* w, const float* b, co
 }
 
 extern "C" size_t tal_linear_workspace_bytes(int64_t M, int N, int K) {
-    return (M > 512 && K % 32 == 0 && K >= 256 && N > 0) ? gemm_splitk_ws_bytes() : 0;
+    return gemm_wants_scratch(M, N, K) ? gemm_splitk_ws_bytes() : 0;
 }
 
 extern "C" int tal_linear_ws_fwd(const float* x, const float* w, const float* b, const float* res, float alpha, int mode,

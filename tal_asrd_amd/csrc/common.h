@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "../../include/tal_asrd.h"
+#include "gemm_plan.h"
 
 namespace tal {
 
@@ -33,8 +34,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // fp32 -> (hi, lo) fp16 pair of the fp16x3 operand form: hi = fp16(x), lo = fp16((x - hi) * 2^11).  Both halves are
 // clamped to the finite fp16 range, so an activation beyond +-65504 degrades gracefully instead of becoming inf.
@@ -215,11 +214,11 @@ struct GemmArgs {
 };
 // mode 0: acc+b | 1: relu(acc+b) | 2: res + alpha*(acc+b) | 3: alpha*(acc+b) | 4: row arg-max partials of acc+b
 int launch_gemm(GemmArgs g, int mode, int nbatch, hipStream_t s);
-// fp16x3 layer on 256 x 160 tiles, one wave per SIMD (gemm_w64.hip); splitk: grid = [whole tiles | K slices of the tail tiles]
-void launch_gemm_w64(const GemmArgs& g, int mode, bool splitk, dim3 grid, hipStream_t s);
-// fp16x3 relu / residual layer on 64 x 80 tiles for short inputs (gemm_s64.hip): whole tiles only, no K slices
-bool gemm_s64_ok(const GemmArgs& g, int mode);
-void launch_gemm_s64(GemmArgs g, int mode, hipStream_t s);
+// one step of launch_gemm's plan (gemm_plan.h) on the kernels of gemm_w64.hip (fp16x3 layer on 256 x 160 tiles, one wave per SIMD;
+// splitk: grid = [whole tiles | K slices of the tail tiles]) and gemm_s64.hip (fp16x3 relu / residual layer on 64 x 80 tiles for
+// short inputs: whole tiles only); g carries the step's rows and tile geometry
+void launch_gemm_w64(const GemmArgs& g, int mode, const GemmStep& st, hipStream_t s);
+void launch_gemm_s64(const GemmArgs& g, int mode, const GemmStep& st, hipStream_t s);
 int gemm_mode4_partials(int64_t M, int N);
 // Y [M, N] (row pitch ldy) = A [M, K] (row pitch lda) . W^T + bias through launch_gemm: the logits of the streaming heads' generic forms
 inline int launch_linear_ld(const float* a, int64_t lda, const float* w, const float* bias, int64_t M, int N, int K, float* y, int64_t ldy,
@@ -251,10 +250,7 @@ int lm_head_project(const char* who, const float* h, int64_t M, int64_t ldh, int
         set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, head + need);
         return TAL_ENOMEM;
     }
-    GemmArgs g = {};
-    g.nb2 = 1;
-    g.A = h; g.W = proj_t; g.Y = t; g.M = M; g.N = E0; g.K = D; g.lda = ldh; g.ldw = D; g.ldy = E0;
-    rc = launch_gemm(g, 0, 1, s);
+    rc = launch_linear_ld(h, ldh, proj_t, nullptr, M, E0, D, t, E0, s);
     if (rc) return rc;
     return stage(t, reinterpret_cast<char*>(workspace) + head, workspace_bytes - head);
 }

@@ -1,10 +1,25 @@
 // Shared pieces of the dense-layer kernels (gemm_f32.hip, gemm_w64.hip): the epilogues and the XCD-aware tile order.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace tal {
 
 constexpr int BK = 32;
+
+// run-time epilogue mode -> template argument: f(std::integral_constant<int, MODE>()).  A caller whose kernels stop short of mode 4
+// (or cover modes 1 and 2 only) leaves the other instantiations out with `if constexpr`; launch_gemm has checked 0 <= mode <= 4.
+template <class F>
+static inline void with_mode(int mode, F&& f) {
+    switch (mode) {
+        case 0: f(std::integral_constant<int, 0>()); break;
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 3: f(std::integral_constant<int, 3>()); break;
+        default: f(std::integral_constant<int, 4>()); break;
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // shared epilogue

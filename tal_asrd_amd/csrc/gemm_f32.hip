@@ -398,17 +398,6 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const GemmArgs g) {
     gemm_epilogue<MODE, NSUB>(g, acc, lds, Y, bias, res, m0, n0, lane, w, wm, wn);
 }
 
-template <int WAVES_M, int NSUB, int BKT>
-static void launch_tile(const GemmArgs& g, int mode, dim3 grid, hipStream_t s) {
-    switch (mode) {
-        case 0: hipLaunchKernelGGL((gemm_nt_f32_kernel<0, WAVES_M, NSUB, BKT>), grid, dim3(256), 0, s, g); break;
-        case 1: hipLaunchKernelGGL((gemm_nt_f32_kernel<1, WAVES_M, NSUB, BKT>), grid, dim3(256), 0, s, g); break;
-        case 2: hipLaunchKernelGGL((gemm_nt_f32_kernel<2, WAVES_M, NSUB, BKT>), grid, dim3(256), 0, s, g); break;
-        case 3: hipLaunchKernelGGL((gemm_nt_f32_kernel<3, WAVES_M, NSUB, BKT>), grid, dim3(256), 0, s, g); break;
-        default: hipLaunchKernelGGL((gemm_nt_f32_kernel<4, WAVES_M, NSUB, BKT>), grid, dim3(256), 0, s, g); break;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // latency kernel for the decoder's short problems (M <= 512): 32 x 32 output tile per workgroup,
 // the four waves split K between them (intra-workgroup split-K, reduced through LDS in a fixed
@@ -525,16 +514,6 @@ __global__ __launch_bounds__(64 * NW) void gemm_splitk4_kernel(const GemmArgs g)
     }
 }
 
-static void launch_splitk4(const GemmArgs& g, int mode, dim3 grid, hipStream_t s) {
-    // (8 waves splitting K were measured for the decoder's K = 2048 layer: 15.6 vs 16.4 us, not worth a variant)
-    switch (mode) {
-        case 0: hipLaunchKernelGGL((gemm_splitk4_kernel<0, 4>), grid, dim3(256), 0, s, g); break;
-        case 1: hipLaunchKernelGGL((gemm_splitk4_kernel<1, 4>), grid, dim3(256), 0, s, g); break;
-        case 2: hipLaunchKernelGGL((gemm_splitk4_kernel<2, 4>), grid, dim3(256), 0, s, g); break;
-        default: hipLaunchKernelGGL((gemm_splitk4_kernel<3, 4>), grid, dim3(256), 0, s, g); break;
-    }
-}
-
 // fix-up of the split-K tail: FIX_PARTS workgroups per tail tile (32 rows each), slices added in ascending
 // order.  All slice loads of a position are issued before the first add; 16-byte loads and stores.
 template <int MODE, int NSUB, int BM = 128>
@@ -610,62 +589,48 @@ __global__ __launch_bounds__(256) void gemm_splitk_fixup_kernel(const GemmArgs g
     }
 }
 
-template <int NSUB, int BM = 128>
-static void launch_fixup(const GemmArgs& g, int mode, dim3 grid, hipStream_t s) {
-    switch (mode) {
-        case 0: hipLaunchKernelGGL((gemm_splitk_fixup_kernel<0, NSUB, BM>), grid, dim3(256), 0, s, g); break;
-        case 1: hipLaunchKernelGGL((gemm_splitk_fixup_kernel<1, NSUB, BM>), grid, dim3(256), 0, s, g); break;
-        case 2: hipLaunchKernelGGL((gemm_splitk_fixup_kernel<2, NSUB, BM>), grid, dim3(256), 0, s, g); break;
-        default: hipLaunchKernelGGL((gemm_splitk_fixup_kernel<3, NSUB, BM>), grid, dim3(256), 0, s, g); break;
-    }
-}
+size_t gemm_splitk_ws_bytes() { return (size_t)1024 * 128 * 160 * sizeof(float); }  // 1024 tail tiles x slices (84 MB of scratch)
 
-
-constexpr int SPLITK_MAX_SLICES = 1024;  // tail tiles x slices (84 MB of scratch)
-size_t gemm_splitk_ws_bytes() { return (size_t)SPLITK_MAX_SLICES * 128 * 160 * sizeof(float); }
-
-template <int MODE, int NSUB, bool SPLITK>
-static void launch_glds_stage(const GemmArgs& g, dim3 grid, hipStream_t s) {
-    // the buffer form of the operand loads (default) needs the tile's lane offsets to fit 32 bits
-    const int want = opt(OPT_GEMM_GLOBAL_LOADS) ? 0 : 2;
-    if (g.f16x3) {
-        if constexpr (MODE == 1 || MODE == 2) {
-            // the TDS block's layers: split-form output under the range guard (MODE 2: split-form residual too)
-            const bool y_ok = g.ldy % 4 == 0 && g.ldy < (1 << 21) && (reinterpret_cast<uintptr_t>(g.Y) & 15) == 0 && g.N % (32 * NSUB) == 0;
-            const bool r_ok = MODE != 2 || (g.res_split && g.ldres % 4 == 0 && g.ldres < (1 << 21) && (reinterpret_cast<uintptr_t>(g.res) & 15) == 0);
-            if (g.out_split && g.range_flag && y_ok && r_ok && grid.y == 1) {
-                hipLaunchKernelGGL((gemm_glds_kernel<MODE, NSUB, SPLITK, 2, true, 1>), grid, dim3(256), 0, s, g);
-                return;
-            }
+// One step of the plan (gemm_plan.h) -> its kernel instantiation; g carries the step's rows and tile geometry.  Kernels without a mode-4
+// form are never planned for it (M3); the split epilogue and the 96-wide tiles exist for modes 1 / 2 only (E; st.epi is set for no other).  A K-sliced
+// step is followed by the fix-up launch: ordered sum of the slices + epilogue, 32 rows per workgroup.
+static void launch_step(const GemmArgs& g, int mode, const GemmStep& st, hipStream_t s) {
+    const dim3 grid(st.grid_x, st.grid_y), fix(st.fixup_grid), b(256);
+    with_mode(mode, [&](auto m) {
+        constexpr int MODE = decltype(m)::value, M3 = MODE < 3 ? MODE : 3, E = MODE == 1 || MODE == 2;
+        // gemm_glds_kernel: fp16x3 with the split or the shared epilogue; exact fp32 with the buffer (default) or the global form of the loads
+        auto glds = [&](auto md, auto nsub, auto sk) {
+            constexpr int MD = decltype(md)::value, NSUB = decltype(nsub)::value, EP = MD == 1 || MD == 2;
+            constexpr bool SK = decltype(sk)::value;
+            constexpr bool F = MD <= 3;         // the modes that have an fp16x3 form (launch_gemm refuses it for mode 4)
+            if (F && g.f16x3 && st.epi) hipLaunchKernelGGL((gemm_glds_kernel<MD, NSUB, SK, 2, F, EP>), grid, b, 0, s, g);
+            else if (F && g.f16x3) hipLaunchKernelGGL((gemm_glds_kernel<MD, NSUB, SK, 2, F>), grid, b, 0, s, g);
+            else if (st.stage == 2) hipLaunchKernelGGL((gemm_glds_kernel<MD, NSUB, SK, 2>), grid, b, 0, s, g);
+            else hipLaunchKernelGGL((gemm_glds_kernel<MD, NSUB, SK, 0>), grid, b, 0, s, g);
+        };
+        using std::integral_constant;
+        switch (st.kernel) {
+            case GK_S64: launch_gemm_s64(g, mode, st, s); break;
+            case GK_W64:
+                launch_gemm_w64(g, mode, st, s);
+                if (st.splitk) hipLaunchKernelGGL((gemm_splitk_fixup_kernel<M3, 5, 256>), fix, b, 0, s, g);
+                break;
+            case GK_GLDS:
+                if (st.nsub == 3) {
+                    if constexpr (E) glds(m, integral_constant<int, 3>(), std::false_type());
+                } else if (!st.splitk) glds(m, integral_constant<int, 5>(), std::false_type());
+                else {
+                    glds(integral_constant<int, M3>(), integral_constant<int, 5>(), std::true_type());      // whole tiles, then K slices -> scratch
+                    hipLaunchKernelGGL((gemm_splitk_fixup_kernel<M3, 5>), fix, b, 0, s, g);
+                }
+                break;
+            // (8 waves splitting K were measured for the decoder's K = 2048 layer: 15.6 vs 16.4 us, not worth a variant)
+            case GK_SPLITK4: hipLaunchKernelGGL((gemm_splitk4_kernel<M3, 4>), grid, b, 0, s, g); break;
+            case GK_TILE_K256: hipLaunchKernelGGL((gemm_nt_f32_kernel<MODE, 1, 1, 128>), grid, b, 0, s, g); break;
+            case GK_TILE_SMALL: hipLaunchKernelGGL((gemm_nt_f32_kernel<MODE, 1, 1, 32>), grid, b, 0, s, g); break;
+            default: hipLaunchKernelGGL((gemm_nt_f32_kernel<MODE, 4, 5, 32>), grid, b, 0, s, g); break;
         }
-        if constexpr (MODE <= 3) hipLaunchKernelGGL((gemm_glds_kernel<MODE, NSUB, SPLITK, 2, true>), grid, dim3(256), 0, s, g);
-        return;
-    }
-    if (want == 2 && g.lda < (1 << 21) && g.ldw < (1 << 21))
-        hipLaunchKernelGGL((gemm_glds_kernel<MODE, NSUB, SPLITK, 2>), grid, dim3(256), 0, s, g);
-    else
-        hipLaunchKernelGGL((gemm_glds_kernel<MODE, NSUB, SPLITK, 0>), grid, dim3(256), 0, s, g);
-}
-
-// splitk: the grid is [whole-round tiles | K slices of the remaining tiles] (modes 0..3 only)
-template <int NSUB>
-static void launch_glds(const GemmArgs& g, int mode, bool splitk, dim3 grid, hipStream_t s) {
-    if (splitk) {
-        switch (mode) {
-            case 0: launch_glds_stage<0, NSUB, true>(g, grid, s); break;
-            case 1: launch_glds_stage<1, NSUB, true>(g, grid, s); break;
-            case 2: launch_glds_stage<2, NSUB, true>(g, grid, s); break;
-            default: launch_glds_stage<3, NSUB, true>(g, grid, s); break;
-        }
-        return;
-    }
-    switch (mode) {
-        case 0: launch_glds_stage<0, NSUB, false>(g, grid, s); break;
-        case 1: launch_glds_stage<1, NSUB, false>(g, grid, s); break;
-        case 2: launch_glds_stage<2, NSUB, false>(g, grid, s); break;
-        case 3: launch_glds_stage<3, NSUB, false>(g, grid, s); break;
-        default: launch_glds_stage<4, NSUB, false>(g, grid, s); break;
-    }
+    });
 }
 
 int launch_gemm(GemmArgs g, int mode, int nbatch, hipStream_t s) {
@@ -688,181 +653,59 @@ int launch_gemm(GemmArgs g, int mode, int nbatch, hipStream_t s) {
     TAL_CHECK_ARG(!g.res_split || (g.f16x3 && mode == 2 && g.N % 160 == 0 && g.ldres % 32 == 0 && g.ldy < (1 << 21) && g.ldres < (1 << 21) &&
                                   (reinterpret_cast<uintptr_t>(g.res) & 15) == 0 && (reinterpret_cast<uintptr_t>(g.Y) & 15) == 0),
                   "gemm: a split-form residual needs the fp16x3 form, mode 2, N %% 160 == 0");
-    // short inputs: 64 x 80 tiles, whole tiles only (gemm_s64.hip), while they fit one round of two workgroups per CU (measured
-    // against the K-sliced launches below: ahead up to 470 / 336 / 432 tiles at N = K = 800 / 1120 / 1440, behind from 590 / 658 / 846,
-    // profiles/r3_gemm_short_inputs.txt)
-    if (g.f16x3 && nbatch == 1 && cdiv(g.M, 64) * (g.N / 80) <= (int64_t)opt(OPT_GEMM_S64_BELOW) * device_cus() &&
-        gemm_s64_ok(g, mode)) {
-        ProfScope prof(PROF_GEMM, 2.0 * (double)g.M * (double)g.N * (double)g.K, s);
-        launch_gemm_s64(g, mode, s);
-        TAL_CHECK_LAUNCH("gemm (64 x 80 tiles)");
-        return TAL_OK;
+    // what to launch is decided in gemm_plan.h from these facts alone (the options: relaxed atomic loads, once per call)
+    auto lo = [](const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15); };
+    GemmCall c = {};
+    c.M = g.M; c.N = g.N; c.K = g.K; c.mode = mode; c.nbatch = nbatch;
+    c.f16x3 = g.f16x3 != 0; c.out_split = g.out_split != 0; c.res_split = g.res_split != 0;
+    c.lda = g.lda; c.ldw = g.ldw; c.ldy = g.ldy; c.ldres = g.ldres;
+    c.has_ws = g.splitk_ws != nullptr; c.has_range_flag = g.range_flag != nullptr;
+    c.a_lo = lo(g.A); c.w_lo = lo(g.W); c.y_lo = lo(g.Y); c.res_lo = lo(g.res); c.bias_lo = lo(g.bias);
+    c.splitk_ws_bytes = g.splitk_ws_bytes;
+    c.cus = device_cus();
+    c.o = {opt(OPT_GEMM_S64_BELOW), opt(OPT_GEMM_NO_W64), opt(OPT_GEMM_NO_GLDS), opt(OPT_GEMM_NO_SPLITK4), opt(OPT_GEMM_NO_SPLITK_TAIL),
+           opt(OPT_GEMM_NO_ROW_SPLIT), opt(OPT_GEMM_NO_N96), opt(OPT_GEMM_GLOBAL_LOADS), opt(OPT_GEMM_S64_ROWS), opt(OPT_GEMM_S64_ORDER),
+           opt(OPT_GEMM_W64_STAGGER)};
+    const GemmPlan plan = gemm_plan(c);
+    TAL_CHECK_ARG(!plan.grid_too_large, "gemm: grid too large");
+    for (int i = 0; i < plan.n; ++i) {
+        const GemmStep& st = plan.step[i];
+        GemmArgs h = g;                 // the step's rows (a row split: rows are independent) and tile geometry
+        h.M = st.rows;
+        h.A = g.A + st.row0 * g.lda;
+        h.Y = g.Y ? g.Y + st.row0 * g.ldy : nullptr;
+        h.res = g.res ? g.res + st.row0 * g.ldres : nullptr;
+        h.tiles_n = st.tiles_n; h.tiles_n_magic = st.tiles_n_magic;
+        h.tiles_m = st.tiles_m; h.tiles_m_magic = st.tiles_m_magic;
+        h.n_major = st.n_major;
+        h.tile_base = st.tile_base; h.split = st.split; h.tail_tiles = st.tail_tiles;
+        h.stagger_ticks = st.stagger_ticks; h.stagger_blocks = st.stagger_blocks;
+        ProfScope prof(PROF_GEMM, st.work, s);
+        launch_step(h, mode, st, s);
+        TAL_CHECK_LAUNCH(st.kernel == GK_S64 ? "gemm (64 x 80 tiles)" : st.kernel == GK_W64 ? "gemm (256 x 160 tiles)" : "gemm");
     }
-    // fp16x3 launches with at least one full round of 256 x 160 tiles (one workgroup per CU) take the one-wave-per-SIMD
-    // kernel (gemm_w64.hip); the tiles of its last partial round are cut along K like the 128 x 160 kernel's
-    if (g.f16x3 && nbatch == 1 && !opt(OPT_GEMM_NO_W64) && !opt(OPT_GEMM_NO_GLDS) &&
-        ((reinterpret_cast<uintptr_t>(g.A) | reinterpret_cast<uintptr_t>(g.W)) & 15) == 0) {
-        const int64_t slots = device_cus();
-        GemmArgs h = g;
-        h.tiles_n = (int)cdiv(g.N, 160);
-        h.tiles_n_magic = h.tiles_n > 1 ? (unsigned)((1ull << 32) / (unsigned)h.tiles_n) + 1u : 0u;
-        const int64_t nb = cdiv(g.M, 256) * h.tiles_n;
-        if (nb >= slots && nb < (1ll << 31) && nb * h.tiles_n < (1ll << 32)) {
-            // ONE full round and a remainder of a few thousand rows (a 5-minute clip's first stage: 295 tiles): the rows of the
-            // whole round's row blocks run here, the rest goes back through this dispatcher as a launch of its own (64 x 80 or
-            // 128 x 96 / 160 tiles) -- K slices of the 39 leftover tiles plus their fix-up launch cost 34 us on top of the
-            // round's 45, the second launch ~16.  Rows are independent: results do not change.
-            const int64_t rb = slots / h.tiles_n, rows1 = rb * 256;
-            if (nb < 2 * slots && nb % slots != 0 && g.M - rows1 > 128 && g.M - rows1 <= 4096 && !opt(OPT_GEMM_NO_ROW_SPLIT)) {
-                {
-                    ProfScope prof(PROF_GEMM, 2.0 * (double)rows1 * (double)g.N * (double)g.K, s);
-                    GemmArgs a = h;
-                    a.M = rows1;
-                    launch_gemm_w64(a, mode, false, dim3((unsigned)(rb * h.tiles_n)), s);
-                    TAL_CHECK_LAUNCH("gemm (256 x 160 tiles)");
-                }
-                GemmArgs r = g;
-                r.M = g.M - rows1;
-                r.A = g.A + rows1 * g.lda;
-                r.Y = g.Y ? g.Y + rows1 * g.ldy : nullptr;
-                r.res = g.res ? g.res + rows1 * g.ldres : nullptr;
-                return launch_gemm(r, mode, 1, s);
-            }
-            ProfScope prof(PROF_GEMM, 2.0 * (double)g.M * (double)g.N * (double)g.K, s);
-            const int64_t rem = nb % slots, full = nb - rem;
-            const int nk = g.K / BK;
-            int split = 0;
-            if (rem > 0 && g.splitk_ws && !opt(OPT_GEMM_NO_SPLITK_TAIL)) {
-                // as below: slice rounds + scratch traffic (a slice writes and the fix-up re-reads a 256 x 160 fp32 tile) against
-                // one more round (measured: ~1.5 us per K step + ~12 us per tile, scripts/ubench/gemm_f16x3_w64.hip)
-                const double round_us = 1.5 * nk + 12.0;
-                double best = 0.97;
-                for (int sp = 2; sp <= 8 && sp <= nk / 4; ++sp) {
-                    if ((size_t)rem * sp * 256 * 160 * sizeof(float) > g.splitk_ws_bytes) break;
-                    const double traffic_us = (double)rem * sp * (2.0 * 256 * 160 * 4) / 4.0e6;
-                    const double tail = (double)cdiv(rem * sp, slots) / sp + traffic_us / round_us;
-                    if (tail < best) { best = tail; split = sp; }
-                }
-            }
-            if (split < 2) {
-                launch_gemm_w64(h, mode, false, dim3((unsigned)nb), s);
-            } else {
-                h.tile_base = (int)full;
-                h.split = split;
-                h.tail_tiles = (int)rem;
-                launch_gemm_w64(h, mode, true, dim3((unsigned)(full + rem * split)), s);
-                launch_fixup<5, 256>(h, mode, dim3((unsigned)rem * 8), s);
-            }
-            TAL_CHECK_LAUNCH("gemm (256 x 160 tiles)");
-            return TAL_OK;
-        }
-    }
-    const bool small = g.M <= 512 && !g.f16x3;
-    const int bm = small ? 32 : 128, bn = small ? 128 : 160;
-    g.tiles_n = (int)cdiv(g.N, bn);
-    g.tiles_n_magic = g.tiles_n > 1 ? (unsigned)((1ull << 32) / (unsigned)g.tiles_n) + 1u : 0u;
-    const int64_t nb = cdiv(g.M, bm) * g.tiles_n;
-    TAL_CHECK_ARG(nb < (1ll << 31) && nb * g.tiles_n < (1ll << 32), "gemm: grid too large");
-    dim3 grid((unsigned)nb, (unsigned)nbatch);
-    ProfScope prof(PROF_GEMM, 2.0 * (double)g.M * (double)g.N * (double)g.K * nbatch, s);
-    const bool aligned16 = ((reinterpret_cast<uintptr_t>(g.A) | reinterpret_cast<uintptr_t>(g.W)) & 15) == 0;
-    // measurement switches (tal_set_option; three relaxed atomic loads per launch)
-    const bool no_splitk4 = opt(OPT_GEMM_NO_SPLITK4) != 0, no_glds = opt(OPT_GEMM_NO_GLDS) != 0, no_tail = opt(OPT_GEMM_NO_SPLITK_TAIL) != 0;
-    // small problems are latency-bound (a K step costs one L2 round trip, not its 16 MFMAs): a
-    // 128-deep K slab quarters the number of dependent round trips
-    if (small && mode != 4 && aligned16 && !no_splitk4) {
-        GemmArgs h = g;
-        h.tiles_n = (int)cdiv(g.N, 32);
-        const int64_t nb2 = cdiv(g.M, 32) * h.tiles_n;
-        TAL_CHECK_ARG(nb2 < (1ll << 31), "gemm: grid too large");
-        launch_splitk4(h, mode, dim3((unsigned)nb2, (unsigned)nbatch), s);
-    } else if (small && g.K >= 256)
-        launch_tile<1, 1, 128>(g, mode, grid, s);
-    else if (small)
-        launch_tile<1, 1, 32>(g, mode, grid, s);
-    else if (g.K % BK == 0 && aligned16 && !no_glds) {
-        // (a 128 x 96 tile -- 10.3 instead of 6.2 rounds on the 1-hour stage-3 shape -- was measured at
-        //  +2 %, inside run-to-run noise: the 160-wide tile stays)
-        // Stream-K-lite: 2 workgroups per CU are resident, so a launch proceeds in rounds of 2*CUs
-        // tiles; the tiles of the last, partial round are cut along K into `split` slices each, so that
-        // they occupy the whole chip for a fraction of a round instead of part of it for a whole one
-        // (1-hour stage-3 shape: 3168 tiles = 6.19 rounds).  The slices are blocks of the same launch,
-        // dispatched behind the whole tiles; a fix-up kernel adds them in a fixed order.  `split` is
-        // the one that minimises the tail, ceil(rem*split/slots)/split rounds, within the scratch size.
-        const int64_t slots = 2 * (int64_t)device_cus();
-        const int64_t rem = nb % slots, full = nb - rem;
-        const int nk = g.K / BK;
-        int split = 0;
-        // (a launch with less than a quarter of a round of tiles -- a few hundred rows -- is cut along K as a whole: its
-        //  few tiles become up to 8x as many K slices, so that most of the chip takes part)
-        if (rem > 0 && (full > 0 || 4 * rem <= slots) && nbatch == 1 && mode <= 3 && g.splitk_ws && !no_tail) {
-            // cost of a candidate in rounds: the slices' own rounds + their scratch traffic (each slice
-            // writes and the fix-up re-reads a 128x160 fp32 tile, ~4 TB/s) relative to one round's duration
-            // (measured: 4.45 us per K step + ~14 us per tile, scripts/bench_gemm_fit.py)
-            // (fp16x3 form: 1.56 us per K step + ~10.5 us per tile, scripts/ubench/gemm_f16x3.hip)
-            const double round_us = g.f16x3 ? 1.56 * nk + 10.5 : 4.45 * nk + 14.0;
-            double best = 0.97;
-            for (int sp = 2; sp <= 8 && sp <= nk / 4; ++sp) {
-                if ((size_t)rem * sp * 128 * 160 * sizeof(float) > g.splitk_ws_bytes) break;
-                const double traffic_us = (double)rem * sp * (2.0 * 128 * 160 * 4) / 4.0e6;
-                const double tail = (double)cdiv(rem * sp, slots) / sp + traffic_us / round_us;
-                if (tail < best) { best = tail; split = sp; }
-            }
-        }
-        // One partial round of 160-wide tiles that already puts two workgroups on some CUs (256 < tiles <= 512) runs as long as
-        // a full one.  When N is a multiple of 96 and the 5/3 as many 96-wide tiles still fit the round, they finish in ~0.6 of
-        // it with every CU busy (5-minute clip, stage 3: 270 -> 450 tiles).  Same MFMA chain per output: bit-identical results.
-        // Cost per K step of a round, us (scripts/bench_gemm_short.py): 0.82 with one workgroup per CU, 1.27 with two, x NSUB / 5.
-        bool n96 = false;
-        int64_t nb3 = 0;
-        // (only the split-form layers of a TDS block -- the launches launch_glds_stage sends to the static-addressing epilogue; the
-        //  generic epilogue's row / column arithmetic is written for 160- and 32-column waves)
-        const bool epi_ok = g.out_split && g.range_flag && g.ldy % 4 == 0 && g.ldy < (1 << 21) && (reinterpret_cast<uintptr_t>(g.Y) & 15) == 0 &&
-                            (mode != 2 || (g.res_split && g.ldres % 4 == 0 && g.ldres < (1 << 21) && (reinterpret_cast<uintptr_t>(g.res) & 15) == 0));
-        if (split < 2 && epi_ok && g.f16x3 && nbatch == 1 && (mode == 1 || mode == 2) && g.N % 96 == 0 && !opt(OPT_GEMM_NO_N96)) {
-            nb3 = cdiv(g.M, 128) * (g.N / 96);
-            auto cost = [&](int64_t tiles, double scale) {
-                const int64_t fr = tiles / slots, r = tiles % slots;
-                const double two = 10.0 + 1.27 * scale * nk, one = 10.0 + 0.82 * scale * nk;
-                return fr * two + (r == 0 ? 0.0 : (r <= slots / 2 ? one : two));
-            };
-            n96 = nb3 < (1ll << 31) && cost(nb3, 0.6) < 0.95 * cost(nb, 1.0);
-        }
-        if (n96) {
-            GemmArgs h = g;
-            h.tiles_n = g.N / 96;
-            h.tiles_n_magic = h.tiles_n > 1 ? (unsigned)((1ull << 32) / (unsigned)h.tiles_n) + 1u : 0u;
-            if (mode == 1) launch_glds_stage<1, 3, false>(h, dim3((unsigned)nb3), s);
-            else launch_glds_stage<2, 3, false>(h, dim3((unsigned)nb3), s);
-        } else if (split < 2) {
-            launch_glds<5>(g, mode, false, grid, s);
-        } else {
-            GemmArgs h = g;
-            h.tile_base = (int)full;
-            h.split = split;
-            h.tail_tiles = (int)rem;
-            launch_glds<5>(h, mode, true, dim3((unsigned)(full + rem * split)), s);   // whole tiles, then K slices -> scratch
-            launch_fixup<5>(h, mode, dim3((unsigned)rem * 4), s);                                 // ordered sum + epilogue (4 x 32 rows per tile)
-        }
-    }
-    else
-        launch_tile<4, 5, 32>(g, mode, grid, s);
-    TAL_CHECK_LAUNCH("gemm");
     return TAL_OK;
 }
 
-int launch_linear_ws(const float* x, const float* w, const float* b, const float* res, float alpha, int mode, int64_t M,
-                     int N, int K, float* y, float* ws, size_t ws_bytes, hipStream_t s) {
-    TAL_CHECK_ARG(x && w && y, "tal_linear_fwd: null pointer");
+// a dense layer on packed rows: x [M, K], w [N, K], y / res [M, N]
+static GemmArgs linear_args(const void* x, const void* w, const float* b, const float* res, float alpha, int64_t M, int N, int K, void* y,
+                            float* ws, size_t ws_bytes) {
     GemmArgs g = {};
-    g.A = x; g.W = w; g.bias = b; g.res = res; g.Y = y;
+    g.A = reinterpret_cast<const float*>(x); g.W = reinterpret_cast<const float*>(w); g.bias = b; g.res = res;
+    g.Y = reinterpret_cast<float*>(y);
     g.M = M; g.N = N; g.K = K;
     g.lda = K; g.ldw = K; g.ldy = N; g.ldres = N;
     g.nb2 = 1;
     g.alpha = alpha;
     g.splitk_ws = ws;
     g.splitk_ws_bytes = ws_bytes;
-    return launch_gemm(g, mode, 1, s);
+    return g;
+}
+
+int launch_linear_ws(const float* x, const float* w, const float* b, const float* res, float alpha, int mode, int64_t M,
+                     int N, int K, float* y, float* ws, size_t ws_bytes, hipStream_t s) {
+    TAL_CHECK_ARG(x && w && y, "tal_linear_fwd: null pointer");
+    return launch_gemm(linear_args(x, w, b, res, alpha, M, N, K, y, ws, ws_bytes), mode, 1, s);
 }
 
 // fp32 -> hi / lo fp16 split in fp32-row geometry: per row and 32-wide K block, 32 hi halves then 32 lo halves
@@ -902,15 +745,7 @@ int launch_split_f16x3(const float* x, void* out, int64_t rows, int K, hipStream
 int launch_linear_f16x3(const void* xs, const void* wsplit, const float* b, const float* res, float alpha, int mode, int64_t M,
                         int N, int K, void* y, int out_split, float* ws, size_t ws_bytes, hipStream_t s, int* range_flag, int res_split) {
     TAL_CHECK_ARG(xs && wsplit && y, "linear_f16x3: null pointer");
-    GemmArgs g = {};
-    g.A = reinterpret_cast<const float*>(xs); g.W = reinterpret_cast<const float*>(wsplit); g.bias = b; g.res = res;
-    g.Y = reinterpret_cast<float*>(y);
-    g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldy = N; g.ldres = N;
-    g.nb2 = 1;
-    g.alpha = alpha;
-    g.splitk_ws = ws;
-    g.splitk_ws_bytes = ws_bytes;
+    GemmArgs g = linear_args(xs, wsplit, b, res, alpha, M, N, K, y, ws, ws_bytes);
     g.f16x3 = 1;
     g.out_split = out_split;
     g.range_flag = range_flag;
@@ -923,14 +758,7 @@ int gemm_mode4_partials(int64_t M, int N) { return M <= 512 ? (int)cdiv(N, 128) 
 
 int launch_linear(const float* x, const float* w, const float* b, const float* res, float alpha, int mode, int64_t M,
                   int N, int K, float* y, hipStream_t s) {
-    TAL_CHECK_ARG(x && w && y, "tal_linear_fwd: null pointer");
-    GemmArgs g = {};
-    g.A = x; g.W = w; g.bias = b; g.res = res; g.Y = y;
-    g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldy = N; g.ldres = N;
-    g.nb2 = 1;
-    g.alpha = alpha;
-    return launch_gemm(g, mode, 1, s);
+    return launch_linear_ws(x, w, b, res, alpha, mode, M, N, K, y, nullptr, 0, s);
 }
 
 }  // namespace tal

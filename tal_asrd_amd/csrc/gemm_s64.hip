@@ -280,40 +280,16 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) void gemm_s64_kernel(co
     if (g.out_split && g.range_flag) note_range(row_ok ? amax : 0.f, g.range_flag);
 }
 
-// M, N, K, leading dimensions and pointers as launch_gemm checked them for the fp16x3 form; N % 80 == 0
-bool gemm_s64_ok(const GemmArgs& g, int mode) {
-    if (!(mode == 1 || mode == 2) || !g.f16x3 || g.N % S_BN != 0 || g.K % BK != 0) return false;
-    if (((reinterpret_cast<uintptr_t>(g.A) | reinterpret_cast<uintptr_t>(g.W) | reinterpret_cast<uintptr_t>(g.Y)) & 15) != 0) return false;
-    if (g.bias && (reinterpret_cast<uintptr_t>(g.bias) & 15) != 0) return false;
-    if (g.ldy % 4 != 0 || g.lda >= (1 << 21) || g.ldw >= (1 << 21)) return false;
-    if (mode == 2 && (!g.res || (reinterpret_cast<uintptr_t>(g.res) & 15) != 0 || g.ldres % 4 != 0)) return false;
-    if ((g.out_split && g.N % 32 != 0) || (mode == 2 && g.res_split && g.ldres % 32 != 0)) return false;
-    return true;
-}
-
-void launch_gemm_s64(GemmArgs g, int mode, hipStream_t s) {
-    g.tiles_n = g.N / S_BN;
-    g.tiles_n_magic = g.tiles_n > 1 ? (unsigned)((1ull << 32) / (unsigned)g.tiles_n) + 1u : 0u;
-    // 32-row tiles (two waves per workgroup) while even those leave CUs idle: stage 3 of a 30-second clip is 108 tiles of 64 rows
-    // on 256 CUs, 216 of 32.  opt gemm_s64_rows: 1 / 2 force 64 / 32 rows.
-    const int rows_opt = opt(OPT_GEMM_S64_ROWS);
-    const bool half = rows_opt == 2 || (rows_opt == 0 && cdiv(g.M, 32) * g.tiles_n <= (int64_t)device_cus());
-    g.tiles_m = (int)cdiv(g.M, half ? 32 : 64);
-    g.tiles_m_magic = g.tiles_m > 1 ? (unsigned)((1ull << 32) / (unsigned)g.tiles_m) + 1u : 0u;
-    // An XCD (its own L2) takes a contiguous eighth of the tile order.  Fewer rows than columns: W (N x K) is the larger operand,
-    // so the order keeps an XCD on a few W panels; otherwise on a few X panels (measured, profiles/r4_gemm_s64_order_depth.txt:
-    // 30.5 -> 28.8 us per layer pair at 376 rows x 1440, 28.0 -> 26.6 at 751 x 1120; the other way round it loses as much).
-    // opt gemm_s64_order: 1 / 2 force m-major / n-major.
-    const int order = opt(OPT_GEMM_S64_ORDER);
-    g.n_major = order == 1 ? 0 : order == 2 ? 1 : (g.M < (int64_t)g.N ? 1 : 0);
-    const dim3 grid((unsigned)(g.tiles_m * g.tiles_n));
-    if (half) {
-        if (mode == 1) hipLaunchKernelGGL((gemm_s64_kernel<1, 2>), grid, dim3(128), 0, s, g);
-        else hipLaunchKernelGGL((gemm_s64_kernel<2, 2>), grid, dim3(128), 0, s, g);
-    } else {
-        if (mode == 1) hipLaunchKernelGGL((gemm_s64_kernel<1, 4>), grid, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL((gemm_s64_kernel<2, 4>), grid, dim3(256), 0, s, g);
-    }
+// the step's kernel (gemm_plan.h decided that the call fits: gemm_s64_ok; 32-row tiles run two waves per workgroup)
+void launch_gemm_s64(const GemmArgs& g, int mode, const GemmStep& st, hipStream_t s) {
+    const dim3 grid(st.grid_x), block(st.block);
+    with_mode(mode, [&](auto m) {
+        constexpr int MODE = decltype(m)::value;
+        if constexpr (MODE == 1 || MODE == 2) {
+            if (st.waves == 2) hipLaunchKernelGGL((gemm_s64_kernel<MODE, 2>), grid, block, 0, s, g);
+            else hipLaunchKernelGGL((gemm_s64_kernel<MODE, 4>), grid, block, 0, s, g);
+        }
+    });
 }
 
 }  // namespace tal

@@ -274,43 +274,18 @@ __global__ __launch_bounds__(256, 1) void gemm_w64_kernel(const GemmArgs g) {
     finish(std::integral_constant<int, 1>());
 }
 
-template <int MODE, bool SPLITK>
-static void launch_w64_mode(const GemmArgs& g, dim3 grid, hipStream_t s) {
-    if constexpr (MODE == 1 || MODE == 2) {
-        // the TDS block's layers: split-form output under the range guard (MODE 2: split-form residual too)
-        const bool y_ok = g.ldy % 4 == 0 && g.ldy < (1 << 21) && (reinterpret_cast<uintptr_t>(g.Y) & 15) == 0 && g.N % W_BN == 0;
-        const bool r_ok = MODE != 2 || (g.res_split && g.ldres % 4 == 0 && g.ldres < (1 << 21) && (reinterpret_cast<uintptr_t>(g.res) & 15) == 0);
-        if (g.out_split && g.range_flag && y_ok && r_ok) {
-            hipLaunchKernelGGL((gemm_w64_kernel<MODE, SPLITK, 1>), grid, dim3(256), 0, s, g);
-            return;
+// the step's kernel: K-sliced tail or whole tiles only, static-addressing split epilogue (modes 1 / 2: E) or the shared one
+void launch_gemm_w64(const GemmArgs& g, int mode, const GemmStep& st, hipStream_t s) {
+    const dim3 grid(st.grid_x), b(256);
+    with_mode(mode, [&](auto m) {
+        constexpr int MODE = decltype(m)::value, E = MODE == 1 || MODE == 2;
+        if constexpr (MODE <= 3) {
+            if (st.splitk && st.epi) hipLaunchKernelGGL((gemm_w64_kernel<MODE, true, E>), grid, b, 0, s, g);
+            else if (st.splitk) hipLaunchKernelGGL((gemm_w64_kernel<MODE, true, 0>), grid, b, 0, s, g);
+            else if (st.epi) hipLaunchKernelGGL((gemm_w64_kernel<MODE, false, E>), grid, b, 0, s, g);
+            else hipLaunchKernelGGL((gemm_w64_kernel<MODE, false, 0>), grid, b, 0, s, g);
         }
-    }
-    hipLaunchKernelGGL((gemm_w64_kernel<MODE, SPLITK, 0>), grid, dim3(256), 0, s, g);
-}
-
-void launch_gemm_w64(const GemmArgs& g0, int mode, bool splitk, dim3 grid, hipStream_t s) {
-    GemmArgs g = g0;
-    const int pct = opt(OPT_GEMM_W64_STAGGER);
-    if (pct > 0 && grid.x >= 2u * (unsigned)device_cus()) {          // (at least two rounds: one round has nothing to be out of phase with)
-        const double tile_us = 1.39 * (g.K / 32) + 12.0;              // scripts/bench_gemm_f16x3_fit.py: K step + fixed cost per round
-        g.stagger_ticks = (int)(tile_us * pct);                       // us * pct / 100 * 100 ticks per us
-        g.stagger_blocks = device_cus();
-    }
-    if (splitk) {
-        switch (mode) {
-            case 0: launch_w64_mode<0, true>(g, grid, s); break;
-            case 1: launch_w64_mode<1, true>(g, grid, s); break;
-            case 2: launch_w64_mode<2, true>(g, grid, s); break;
-            default: launch_w64_mode<3, true>(g, grid, s); break;
-        }
-        return;
-    }
-    switch (mode) {
-        case 0: launch_w64_mode<0, false>(g, grid, s); break;
-        case 1: launch_w64_mode<1, false>(g, grid, s); break;
-        case 2: launch_w64_mode<2, false>(g, grid, s); break;
-        default: launch_w64_mode<3, false>(g, grid, s); break;
-    }
+    });
 }
 
 }  // namespace tal
