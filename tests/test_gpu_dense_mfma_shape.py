@@ -1,5 +1,5 @@
 """The fp16x3 dense layers on 16x16x32 MFMAs (csrc/gemm_w64.hip, the F16X3 branch of gemm_glds_kernel in csrc/gemm_f32.hip, the
-16x16 staging write of csrc/gemm_common.h), GPU.
+16x16 staging write of csrc/gemm_common.h, the short-input kernel csrc/gemm_s64.hip) and the row split of csrc/gemm_plan.h, GPU.
 
 1. An exact integer model through every dispatch form.  The operands are built on the host directly in the split format with
    small integer halves, so that every partial sum is exact in fp32 whatever the summation order; the expected output is the
@@ -13,6 +13,14 @@ forms -- the split-K scratch, which the slices fill with whole tiles: the number
 tail tiles x slices x tile rows x 160, which tells the 256-row kernel from the 128-row kernel.  For the whole-tile forms
 (256 x 160, 128 x 160, 128 x 96) the kernel is the dispatcher's choice at this tile count (launch_gemm, csrc/gemm_f32.hip);
 each case asserts the inequalities that decide it, with the CU count of the device, and that the scratch stayed untouched.
+
+The short-input kernel (64 x 80 and 32 x 80 tiles) and the row split (one round of 256 x 160 tiles, then a second launch for the
+remaining rows) take their cases from tests/_dense_forms.py: every remainder of the K loop and the short prologue (K / 32 = 1 .. 9),
+grids of every residue mod 8 with and without the magic division, both tile orders, last tiles of 1, 31 and 63 rows, N != K, and
+every epilogue arm (fp32 / split residual; fp32 / guarded split / clamped split output) -- bit for bit against the model and
+against the 128 x 160 kernels (option gemm_s64_below = 0); the row-split cases compare the whole output across the seam in two
+scopes.  Their form is the restated plan of tests/_dense_forms.py (expect_plan), which tests/test_dense_forms_cpu.py holds to
+csrc/gemm_plan.h; it is asserted before a case runs.
 """
 import ctypes as C
 
@@ -20,6 +28,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import _dense_forms as F
 from tests.conftest import has_gpu
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs an MI355X")]
@@ -39,54 +48,20 @@ def _cdiv(a, b):
     return -(-a // b)
 
 
-def _pack(hi, lo):
-    """the fp16x3 operand format (include/tal_asrd.h, _np_split in tests/test_gpu_parity.py): per row and 32-wide K block,
-    32 hi halves then 32 lo halves"""
-    rows, K = hi.shape
-    out = np.empty((rows, K // 32, 64), dtype=np.float16)
-    out[:, :, :32] = hi.reshape(rows, K // 32, 32)
-    out[:, :, 32:] = lo.reshape(rows, K // 32, 32)
-    return out
-
-
-def _host_split(y):
-    """host split of exact fp32 values inside the fp16 range: hi = fp16(y), lo = fp16((y - hi) * 2^11)"""
-    hi = y.astype(np.float16)
-    lo = ((y - hi.astype(np.float32)) * np.float32(2048.0)).astype(np.float16)
-    return _pack(hi, lo)
-
-
-def _int_operand(rng, rows, K):
-    hi = rng.integers(-2, 3, size=(rows, K)).astype(np.float32)
-    lo = rng.integers(-8, 9, size=(rows, K)).astype(np.float32)
-    return hi, lo
+_pack, _host_split, _int_operand = F.pack, F.host_split, F.int_operand
 
 
 def _exact_problem(M, N, K):
-    """operands with integer halves and the exact results of both layers.  Model: y = sum hi.hi' + b + 2^-11 sum (hi.lo' + lo.hi')
-    (lo.lo' is dropped by the kernels by design).  Every term is an integer: the float64 products below are an int64 model,
-    exact in any order; 4 K + 4 < 4096 keeps every fp32 partial sum of the kernel exact too."""
-    assert 4 * K + 4 < 4096
-    rng = np.random.default_rng(1000 * N + K)
-    xh, xl = _int_operand(rng, M, K)
-    wh, wl = _int_operand(rng, N, K)
-    b = rng.integers(-4, 5, size=N).astype(np.float32)
-    rh, rl = _int_operand(rng, M, N)          # the split residual of the mode-2 layer
+    """the exact integer model (tests/_dense_forms.py: exact_model, numpy on the host) with its operands on the device: x, w and
+    the residual in the split format, the bias, and the residual once more as a plain fp32 matrix (rh + rl / 2048, exact)"""
+    m = F.exact_model(M, N, K)
     d = dev()
-    t = lambda a: torch.from_numpy(a).to(d).double()
-    hh = t(xh) @ t(wh).t()
-    xx = t(xh) @ t(wl).t() + t(xl) @ t(wh).t()
-    pre = hh + t(b) + xx / 2048.0
-    assert float(pre.abs().max()) < 4 * K + 8
-    y1 = pre.clamp_min(0.0)
-    y2 = (t(rh) + t(rl) / 2048.0) + 0.5 * pre
-    exp = {}
-    for mode, y in ((1, y1), (2, y2)):
-        y32 = y.float()
-        assert torch.equal(y32.double(), y)                      # the model's values ARE fp32 values
-        exp[mode] = y32.cpu().numpy()
     u8 = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1)).to(d)
-    return dict(xs=u8(_pack(xh, xl)), ws=u8(_pack(wh, wl)), b=torch.from_numpy(b).to(d), rs=u8(_pack(rh, rl)), exp=exp)
+    p = dict(xs=u8(_pack(m["xh"], m["xl"])), ws=u8(_pack(m["wh"], m["wl"])), b=torch.from_numpy(m["b"]).to(d), rf=torch.from_numpy(m["rf"]).to(d),
+             exp=m["exp"])
+    if N % 32 == 0:                          # (no split form of an [M, N] matrix otherwise: fp32 in and out only)
+        p["rs"] = u8(_pack(m["rh"], m["rl"]))
+    return p
 
 
 _PROBLEMS = {}
@@ -103,8 +78,10 @@ def _problem(M, N, K):
 GUARD = 5
 
 
-def _launch(p, M, N, K, mode, out_split, guarded, scratch):
-    """one dense layer; returns (output rows, floats of the split-K scratch that were written, profiling scopes, their work)"""
+def _launch(p, M, N, K, mode, out_split, guarded, scratch, res_form=None):
+    """one dense layer; returns (output rows, floats of the split-K scratch that were written, profiling scopes, their work).
+    res_form of a mode-2 layer: "split" (guarded call only) or "f32"; default: split under the guard, fp32 without it (the
+    unguarded entry point takes no other)"""
     from tal_asrd_amd import _native as N_
     lib = N_.lib()
     d = dev()
@@ -114,16 +91,20 @@ def _launch(p, M, N, K, mode, out_split, guarded, scratch):
         ybuf = torch.full((M + GUARD, N), 4321.0, device=d)
     scratch.fill_(0xFF)                      # NaN as fp32; a K slice writes whole tiles of finite partial sums
     flag = torch.zeros(16, dtype=torch.int32, device=d)
-    res = p["rs"] if mode == 2 else None
+    res, res_split = None, 0
+    if mode == 2:
+        res_split = int((res_form or ("split" if guarded else "f32")) == "split")
+        assert guarded or not res_split
+        res = p["rs"] if res_split else p["rf"]
     lib.tal_prof_reset()
     lib.tal_prof_enable(1)
     try:
         if guarded:
-            N_.check(lib.tal_linear_f16x3_guarded_fwd(N_.ptr(p["xs"]), N_.ptr(p["ws"]), N_.ptr(p["b"]), N_.ptr(res) if res is not None else None,
-                                                      1 if mode == 2 else 0, 0.5, mode, M, N, K, N_.ptr(ybuf), out_split, N_.ptr(flag),
-                                                      N_.ptr(scratch), scratch.numel(), N_.stream_handle()), "tal_linear_f16x3_guarded_fwd")
+            N_.check(lib.tal_linear_f16x3_guarded_fwd(N_.ptr(p["xs"]), N_.ptr(p["ws"]), N_.ptr(p["b"]), N_.ptr(res), res_split, 0.5, mode, M, N, K,
+                                                      N_.ptr(ybuf), out_split, N_.ptr(flag), N_.ptr(scratch), scratch.numel(), N_.stream_handle()),
+                     "tal_linear_f16x3_guarded_fwd")
         else:
-            N_.check(lib.tal_linear_f16x3_fwd(N_.ptr(p["xs"]), N_.ptr(p["ws"]), N_.ptr(p["b"]), None, 0.5, mode, M, N, K, N_.ptr(ybuf), out_split,
+            N_.check(lib.tal_linear_f16x3_fwd(N_.ptr(p["xs"]), N_.ptr(p["ws"]), N_.ptr(p["b"]), N_.ptr(res), 0.5, mode, M, N, K, N_.ptr(ybuf), out_split,
                                               N_.ptr(scratch), scratch.numel(), N_.stream_handle()), "tal_linear_f16x3_fwd")
         torch.cuda.synchronize()
     finally:
@@ -146,7 +127,15 @@ def _launch(p, M, N, K, mode, out_split, guarded, scratch):
 RUNS = [(1, 0, False), (2, 0, True), (1, 1, True), (2, 1, True)]
 
 
-def _check_exact(M, N, K, options, expect_written, runs=RUNS):
+def _where(bad):
+    """rows and columns of a mismatch, for the message (the integer model tells which rows / columns are off)"""
+    r, c = np.nonzero(bad)
+    return "%d elements off; rows %s, columns %s" % (len(r), np.unique(r)[:12].tolist(), np.unique(c)[:12].tolist())
+
+
+def _check_exact(M, N, K, options, expect_written, runs=RUNS, scopes=1):
+    """every run bit for bit against the model, in `scopes` dense launch scopes whose work adds up to the call's.  A run is
+    (mode, split output, guarded call) or (mode, split output, guarded call, residual form)."""
     from tal_asrd_amd import _native as N_
     lib = N_.lib()
     p = _problem(M, N, K)
@@ -155,20 +144,22 @@ def _check_exact(M, N, K, options, expect_written, runs=RUNS):
     try:
         for name, value in options.items():
             N_.set_option(name, value)
-        for mode, out_split, guarded in runs:
-            what = (M, N, K, mode, out_split, guarded)
-            y, written, scopes, work = _launch(p, M, N, K, mode, out_split, guarded, scratch)
-            assert scopes == 1 and work == 2.0 * M * N * K, ("one dense launch scope with the whole work", what, scopes, work)
+        for run in runs:
+            mode, out_split, guarded = run[:3]
+            what = (M, N, K, options) + tuple(run)
+            y, written, nscopes, work = _launch(p, M, N, K, mode, out_split, guarded, scratch, *run[3:])
+            assert nscopes == scopes and work == 2.0 * M * N * K, ("dense launch scopes and their whole work", what, nscopes, work)
             assert written == expect_written(mode, out_split, guarded), ("split-K scratch floats written", what, written)
             if out_split:
-                got = y.cpu().numpy().view(np.uint16)
-                want = _host_split(p["exp"][mode]).view(np.uint16).reshape(-1)
-                assert np.array_equal(got, want), what
+                got = y.cpu().numpy().view(np.uint16).reshape(M, -1)
+                want = _host_split(p["exp"][mode]).view(np.uint16).reshape(M, -1)
+                assert np.array_equal(got, want), (what, _where((got != want).reshape(M, N // 32, 2, 32).any(axis=2).reshape(M, N)))
             else:
-                assert torch.equal(y.cpu(), torch.from_numpy(p["exp"][mode])), what
+                got, want = y.cpu(), torch.from_numpy(p["exp"][mode])
+                assert torch.equal(got, want), (what, _where((got != want).numpy()))
     finally:
         for name in options:
-            N_.set_option(name, {"gemm_s64_below": 2}.get(name, 0))
+            N_.set_option(name, F.OPTION_DEFAULTS.get(name, 0))
 
 
 def _not_short_input(M, N, cus):
@@ -271,3 +262,100 @@ def test_random_data_against_float64(C_):
         err = float((got - ref).abs().max())
         print("dense 16x16x32, M=%d N=K=%d mode %d: max |err| vs float64 %.3e (bound %.3e)" % (M, K, mode, err, bound))
         assert err < bound, (mode, err)
+
+
+# ---- the short-input kernel (gemm_s64_kernel, csrc/gemm_s64.hip) and the row split of gemm_plan ----------------------------------------
+# The cases and the form each is there for: tests/_dense_forms.py.  Which form ran: expect_plan restates the plan (held to
+# csrc/gemm_plan.h in tests/test_dense_forms_cpu.py) and is asserted first, with the CU count of the device, so that a case that left
+# its arm fails loudly; on the device a 64 x 80 launch is one scope with the whole work and no scratch, a row split two scopes.
+
+# One test per table, not one per case (the suite's GPU test count stays close to what it was): a test walks every case, goes on
+# after a case that fails its assertions and names every failed case at the end; any other error ends it at once.
+
+def _walk(cases, check):
+    failed = []
+    for case in cases:
+        try:
+            check(case)
+        except AssertionError as e:
+            failed.append("%s: %s" % (case["id"], " ".join(str(e).split())[:400]))
+    assert not failed, "%d of %d cases failed:\n%s" % (len(failed), len(cases), "\n".join(failed))
+
+
+def test_exact_s64():
+    """every case of short_cases: one launch of gemm_s64_kernel in every epilogue arm (fp32 / split residual, fp32 / guarded split /
+    clamped split output), bit for bit against the integer model; then the same runs with option gemm_s64_below = 0 -- the
+    128 x 160 kernels, which the model is exact for in any summation order -- must give the same bits.  The gemm_s64_rows /
+    gemm_s64_order variants of a shape are compared with the same expected bits, hence with the default run."""
+    cus = _cus()
+
+    def check(case):
+        F.check_short_form(case, cus)
+        M, N, K = case["M"], case["N"], case["K"]
+        runs = F.runs_of(case)
+        _check_exact(M, N, K, case["options"], lambda *run: 0, runs=runs)
+        _check_exact(M, N, K, dict(case["options"], gemm_s64_below=0), lambda *run: 0, runs=runs)
+
+    _walk(F.short_cases(cus), check)
+
+
+def test_exact_row_split():
+    """every case of row_split_cases: one round of 256 x 160 tiles and a second launch (32 x 80, 64 x 80 or 128 x 160 tiles) for the
+    remaining rows, which starts at row rows1 with every pointer moved on: the WHOLE output against the integer model, the rows on
+    both sides of the seam and the last row included.  Two scopes whose work adds up to the call's; no scratch."""
+    cus = _cus()
+
+    def check(case):
+        first, second = F.expect_plan(case, cus)
+        assert first[0] == "w64" and second[0] == case["second"][0] and second[2] == first[1]
+        _check_exact(case["M"], case["N"], case["K"], {}, lambda *run: 0, runs=F.ROW_SPLIT_RUNS, scopes=2)
+
+    _walk(F.row_split_cases(cus), check)          # (row_split_cases asserts the plan's conditions at this CU count)
+
+
+RANDOM_S64 = [(300, 640, 896), (300, 896, 640), (700, 1152, 64), (129, 160, 96), (300, 880, 640), (700, 1120, 64)]
+
+
+def test_random_data_s64_against_float64():
+    """short inputs on random operands at N != K and K / 32 = 28, 20, 2 and 3 (remainders of 0, 2 and 3 K steps of gemm_s64_kernel;
+    the project's widths give 1 and 3 only): operands from ops.split_f16x3, outputs against float64 of the operands' decoded values,
+    bound 2e-5 * max(1, sqrt(K) / 8) (the project's dense-layer bound); two runs, same bits.
+    gemm_s64_kernel takes N % 80 == 0 only (gemm_s64_ok): N = 896 and 1152 -- the widths of SDModel(n_mels=64) -- are no
+    multiples of 80 and run on 128 x 160 tiles with a column tail; 880 and 1120 stand in for them on the 64 x 80 tiles at the same K.
+    Measured max |err| per shape: profiles/dense_mfma_shape.txt section 6."""
+    _walk([dict(id="%dx%dx%d" % s, shape=s) for s in RANDOM_S64], lambda case: _random_s64(*case["shape"]))
+
+
+def _random_s64(M, N, K):
+    from tal_asrd_amd import ops, _native as N_
+    lib = N_.lib()
+    cus = _cus()
+    if N % 80 == 0:
+        assert F.expect_plan(dict(M=M, N=N, K=K), cus)[0][0] == "s64", "no short input at %d CUs" % cus
+    g = torch.Generator().manual_seed(1000 * M + N + K)
+    x = torch.randn(M, K, generator=g).to(dev())
+    w = (torch.randn(N, K, generator=g) / K ** 0.5).to(dev())
+    b = torch.randn(N, generator=g).to(dev())
+    r = torch.randn(M, N, generator=g).to(dev())
+    dec = lambda s, rows: (lambda h: (h[:, :, :32] + h[:, :, 32:] / 2048.0).reshape(rows, -1))(s.view(torch.float16).reshape(rows, -1, 64).double())
+    xs, wsp = ops.split_f16x3(x), ops.split_f16x3(w)
+    p = dict(xs=xs, ws=wsp, b=b, rf=r)
+    runs = [(1, 0, False, None), (2, 0, False, "f32")]
+    if N % 160 == 0:
+        p["rs"] = ops.split_f16x3(r)
+        runs.append((2, 1, True, "split"))
+    scratch = torch.empty(max(int(lib.tal_linear_workspace_bytes(M, N, K)), 16), dtype=torch.uint8, device=dev())
+    pre = dec(xs, M) @ dec(wsp, N).t() + b.double()
+    bound = 2e-5 * max(1.0, K ** 0.5 / 8)
+    for mode, out_split, guarded, res_form in runs:
+        y1, _, scopes, work = _launch(p, M, N, K, mode, out_split, guarded, scratch, res_form)
+        y1 = y1.clone()
+        y2 = _launch(p, M, N, K, mode, out_split, guarded, scratch, res_form)[0]
+        assert scopes == 1 and work == 2.0 * M * N * K
+        assert torch.equal(y1, y2), (mode, "not repeatable")
+        got = dec(y1, M) if out_split else y1.double()
+        ref = pre.clamp_min(0.0) if mode == 1 else (dec(p["rs"], M) if res_form == "split" else r.double()) + 0.5 * pre
+        err = float((got - ref).abs().max())
+        print("dense %s, M=%d N=%d K=%d mode %d out_split %d res %s: max |err| vs float64 %.3e (bound %.3e)" % (
+            "64 x 80" if N % 80 == 0 else "128 x 160", M, N, K, mode, out_split, res_form, err, bound))
+        assert err < bound, (mode, out_split, err)

@@ -34,7 +34,8 @@ SITES = [
      "test_dense_guard[glds160], [glds96], [w64_tail], [w64_rowsplit]"),
     ("gemm_s64.hip", "gemm_s64_kernel", {"note_range": 1, "split_f16x3_pair": 2, "split_f16x3": 1}, "guarded (row_ok mask) and unguarded arm",
      "tal_linear_f16x3_guarded_fwd 1500 x 800 (64 rows), 129 x 800 (32 rows), remainder launch of 13185 x 800",
-     "test_dense_guard[s64], [s64_half], [w64_rowsplit]"),
+     "test_dense_guard[s64], [s64_half], [w64_rowsplit]; values bit for bit in both arms: test_exact_s64, test_exact_row_split "
+     "(tests/test_gpu_dense_mfma_shape.py)"),
     ("gconv.hip", "gconv_s2_c1_kernel", {"note_range": 1, "split_f16x3": 1}, "guarded, clamped",
      "tal_tds_fwd, first resize conv of an all-split stage", "test_tds_sites[split-s0.down]"),
     ("gconv.hip", "gconv_mfma_kernel", {"note_range": 3, "split_f16x3": 10, "split_f16x3_pair": 4}, "guarded (pair) / unguarded (clamped)",
