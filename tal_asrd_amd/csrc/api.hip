@@ -417,14 +417,14 @@ extern "C" size_t tal_tds_workspace_bytes(const tal_tds_desc* d, int B, int64_t 
 // ... its stride-2 resize conv can run on the matrix cores
 static bool tds_s2_mfma_ok(const tal_tds_desc* d, int B, int i, int64_t Tin, int ks, bool general, bool force_f32) {
     return !force_f32 && !general && d->down_w_frag[i] && (int64_t)B * conv_out_len(Tin, ks) > 64 &&
-           gconv_f16x3_weight_bytes(d->channels[i], d->channels[i + 1], d->groups, 2) > 0 && gconv_f16x3_fits(Tin, d->channels[i]);
+           gconv_has_mfma(d->channels[i], d->channels[i + 1], d->groups, 2) && gconv_f16x3_fits(Tin, d->channels[i]);
 }
 // ... its TDSBlocks can keep every activation in the hi / lo split form (`fp32_only`: the exact mode or option tds_fp32_activations)
 static bool tds_blocks_split_ok(const tal_tds_desc* d, int B, int i, int64_t Tin, int ks, bool general, bool fp32_only) {
     if (fp32_only || general || d->depths[i] == 0) return false;
     const int c = d->channels[i + 1];
     const int64_t To = conv_out_len(Tin, ks);
-    if ((int64_t)B * To <= 128 || c % 160 != 0 || c % 32 != 0 || !gconv_f16x3_fits(To, c) || gconv_f16x3_weight_bytes(c, c, d->groups, 1) == 0) return false;
+    if ((int64_t)B * To <= 128 || c % 160 != 0 || c % 32 != 0 || !gconv_f16x3_fits(To, c) || !gconv_has_mfma(c, c, d->groups, 1)) return false;
     for (int j = 0; j < d->depths[i]; ++j)
         if (!d->blocks[i][j].fc0_w_split || !d->blocks[i][j].fc3_w_split || !d->blocks[i][j].conv_w_frag) return false;
     return true;
@@ -543,7 +543,7 @@ static int tds_walk(const tal_tds_desc* d, const float* x, const float* x_mean, 
                     if (!rc) rc = tds_launch_dense(bw, true, true, x1, x1, h, outp, out_split, M, c, skws, s, range_flag);
                 } else {
                     const bool f16x3 = !force_f32 && bw.fc0_w_split && bw.fc3_w_split && M > 128 && c % 160 == 0;
-                    const bool conv_mfma = !force_f32 && !general && M > 64 && bw.conv_w_frag && gconv_f16x3_weight_bytes(c, c, d->groups, 1) > 0 && gconv_f16x3_fits(To, c);
+                    const bool conv_mfma = !force_f32 && !general && M > 64 && bw.conv_w_frag && gconv_has_mfma(c, c, d->groups, 1) && gconv_f16x3_fits(To, c);
                     const bool fuse_split = opt(OPT_GCONV_FUSE_SPLIT) != 0;
                     if (general)
                         rc = launch_gconv_res_k(a, bw.conv_w, bw.conv_b, bw.resweight, B, To, c, d->groups, ks, x1, s);

@@ -8,6 +8,7 @@
 
 #include "../../include/tal_asrd.h"
 #include "gemm_plan.h"
+#include "gconv_plan.h"
 
 namespace tal {
 
@@ -283,7 +284,31 @@ int launch_gconv_s2_k(const float* x, const float* wp, const float* bias, int B,
 int launch_gconv_res_k(const float* x, const float* wp, const float* bias, float alpha, int B, int64_t T, int C, int groups, int ks,
                        float* y, hipStream_t s);
 size_t gconv_f16x3_weight_bytes(int C_in, int C_out, int groups, int stride);
-bool gconv_f16x3_fits(int64_t T, int C);
+// Every grouped-conv launch is decided by gconv_plan (gconv_plan.h).  gconv_call: the facts of a call with the device's CU count and
+// the grouped-conv options filled in; gconv_refused: a refused plan's message, returns TAL_EINVAL (both csrc/gconv.hip).
+GconvCall gconv_call(int entry, int B, int64_t T_in, int C_in, int C_out, int groups, int ks, const void* x);
+int gconv_refused(const GconvCall& c, int why);
+// One planned launch of KERN: its dynamic LDS reserved once per instantiation (beyond the default 64 KB it needs the attribute), the
+// plan's profiling scope around the launch.  `what` names the kernel in the two failure messages.
+template <auto KERN, class... Args>
+int gconv_launch_planned(const GconvLaunch& p, dim3 grid, const char* what, hipStream_t s, Args... args) {
+    static bool reserved = false;
+    if (p.lds_reserve > 0 && !reserved) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_reserve) != hipSuccess) {
+            set_error("%s: cannot reserve %zu bytes of LDS", what, p.lds_reserve);
+            return TAL_EHIP;
+        }
+        reserved = true;
+    }
+    if (p.prof == GCP_NONE) {
+        hipLaunchKernelGGL(KERN, grid, dim3(p.block), p.lds, s, args...);
+    } else {
+        ProfScope prof(p.prof, p.work, s);
+        hipLaunchKernelGGL(KERN, grid, dim3(p.block), p.lds, s, args...);
+    }
+    TAL_CHECK_LAUNCH(what);
+    return TAL_OK;
+}
 // first resize conv (1 -> 10 channels per group) + first TDSBlock conv of the stage in one launch (gconv_mfma_kernel<.., FROMC1>)
 bool gconv_c1_res_fusable(int C_in, int C_out, int groups, const float* mel);
 int launch_gconv_c1_res_f16x3(const float* mel, const float* w1, const float* b1, const float* in_mean, const void* w_frag, const float* bias,

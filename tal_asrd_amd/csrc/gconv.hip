@@ -19,8 +19,6 @@
 
 namespace tal {
 
-constexpr int KS = 21;
-
 template <int CIG, int COG, int STRIDE, int GB, int TT, bool RESID>
 __global__ __launch_bounds__(256) void gconv_kernel(const float* __restrict__ x, const float* __restrict__ wp,
                                                    const float* __restrict__ bias, float alpha,
@@ -233,113 +231,6 @@ __global__ __launch_bounds__(256) void gconv_s2_c1_kernel(const float* __restric
     if (YSPLIT) note_range(amax, range_flag);
 }
 
-template <int CIG, int COG, int STRIDE, int GB, int TT, bool RESID>
-static int launch_spec(const float* x, const float* wp, const float* bias, float alpha, float* y, int B, int64_t T_in,
-                       int64_t T_out, int C_in, int C_out, int groups, hipStream_t s) {
-    constexpr int TIN = (TT - 1) * STRIDE + KS;
-    constexpr int TINP = TIN | 1;
-    constexpr size_t lds = (size_t)GB * CIG * TINP * sizeof(float);
-    auto kern = gconv_kernel<CIG, COG, STRIDE, GB, TT, RESID>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess) {
-            set_error("gconv: cannot reserve %zu bytes of LDS", lds);
-            return TAL_EHIP;
-        }
-        attr_set = true;
-    }
-    dim3 grid((unsigned)cdiv(T_out, TT), (unsigned)(groups / GB), (unsigned)B);
-    ProfScope prof(RESID ? PROF_GCONV_RES : PROF_GCONV_S2, 2.0 * (double)B * (double)T_out * C_out * CIG * KS, s);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, x, wp, bias, alpha, y, T_in, T_out, C_in, C_out);
-    TAL_CHECK_LAUNCH("gconv");
-    return TAL_OK;
-}
-
-template <bool RESID>
-static int launch_generic(const float* x, const float* wp, const float* bias, float alpha, float* y, int B,
-                          int64_t T_in, int64_t T_out, int C_in, int C_out, int groups, int stride, hipStream_t s) {
-    const int64_t total = (int64_t)B * T_out * C_out;
-    if (total == 0) return TAL_OK;
-    hipLaunchKernelGGL(gconv_generic_kernel<RESID>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, x, wp, bias,
-                       alpha, y, T_in, T_out, C_in, C_out, C_in / groups, C_out / groups, stride, total);
-    TAL_CHECK_LAUNCH("gconv_generic");
-    return TAL_OK;
-}
-
-bool gconv_s2_can_split(int C_in, int C_out, int groups, const float* x) {
-    const bool c1_generic = opt(OPT_GCONV_C1_GENERIC) != 0;
-    return groups > 0 && C_in == groups && C_out == 10 * groups && groups % 20 == 0 && C_in % 4 == 0 && C_out % 32 == 0 &&
-           (reinterpret_cast<uintptr_t>(x) & 15) == 0 && !c1_generic;
-}
-
-// the shapes whose first resize conv can take the mean of its input as a bias correction (gconv_s2_c1_kernel)
-bool gconv_s2_can_fold_mean(int C_in, int C_out, int groups, const float* x) {
-    return groups > 0 && C_in == groups && C_out == 10 * groups && groups % 20 == 0 && C_in % 4 == 0 &&
-           (reinterpret_cast<uintptr_t>(x) & 15) == 0 && !opt(OPT_GCONV_C1_GENERIC);
-}
-
-int launch_gconv_s2(const float* x, const float* wp, const float* bias, int B, int64_t T_in, int C_in, int C_out,
-                    int groups, float* y, hipStream_t s, void* y_split, int* range_flag, const float* in_mean) {
-    TAL_CHECK_ARG(x && wp && bias && (y || y_split), "tal_gconv_s2_fwd: null pointer");
-    TAL_CHECK_ARG(!in_mean || gconv_s2_can_fold_mean(C_in, C_out, groups, x), "tal_gconv_s2_fwd: no mean-folding kernel for this shape");
-    TAL_CHECK_ARG(!y_split || gconv_s2_can_split(C_in, C_out, groups, x), "tal_gconv_s2_fwd: no split-output kernel for this shape");
-    TAL_CHECK_ARG(groups > 0 && C_in % groups == 0 && C_out % groups == 0, "tal_gconv_s2_fwd: channels %d->%d not divisible by groups %d", C_in, C_out, groups);
-    TAL_CHECK_ARG(B > 0 && T_in >= KS, "tal_gconv_s2_fwd: T_in=%lld shorter than the kernel", (long long)T_in);
-    const int64_t T_out = (T_in - KS) / 2 + 1;
-    const int cig = C_in / groups, cog = C_out / groups;
-    const bool c1_generic = opt(OPT_GCONV_C1_GENERIC) != 0;
-    if (cig == 1 && cog == 10 && groups % 20 == 0 && C_in % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && !c1_generic) {
-        // channel-major lanes: coalesced 256-byte stores (0.29 -> 0.16 ms on the 1-hour shape)
-        constexpr int NG = 20, TT = 256, TTS = 32;
-        ProfScope prof(PROF_GCONV_S2, 2.0 * (double)B * (double)T_out * C_out * KS, s);
-        // a lane walks its tile's time steps one after the other: short inputs (a 30-second clip is 6 tiles of 256 steps x 4
-        // group blocks = 24 workgroups, 42 us) take 32-step tiles so that the launch covers the chip
-        const bool small = cdiv(T_out, TT) * (groups / NG) * B < 256;
-        dim3 grid((unsigned)cdiv(T_out, small ? TTS : TT), (unsigned)(groups / NG), (unsigned)B);
-        float* yo = y_split ? reinterpret_cast<float*>(y_split) : y;
-        if (y_split && small)
-            hipLaunchKernelGGL((gconv_s2_c1_kernel<10, NG, TTS, true>), grid, dim3(256), 0, s, x, wp, bias, yo, T_in, T_out, C_in, C_out, range_flag, in_mean);
-        else if (y_split)
-            hipLaunchKernelGGL((gconv_s2_c1_kernel<10, NG, TT, true>), grid, dim3(256), 0, s, x, wp, bias, yo, T_in, T_out, C_in, C_out, range_flag, in_mean);
-        else if (small)
-            hipLaunchKernelGGL((gconv_s2_c1_kernel<10, NG, TTS, false>), grid, dim3(256), 0, s, x, wp, bias, yo, T_in, T_out, C_in, C_out, range_flag, in_mean);
-        else
-            hipLaunchKernelGGL((gconv_s2_c1_kernel<10, NG, TT, false>), grid, dim3(256), 0, s, x, wp, bias, yo, T_in, T_out, C_in, C_out, range_flag, in_mean);
-        TAL_CHECK_LAUNCH("gconv (1 channel per group)");
-        return TAL_OK;
-    }
-    if (cig == 1 && cog == 10 && groups % 16 == 0)
-        return launch_spec<1, 10, 2, 16, 128, false>(x, wp, bias, 0.f, y, B, T_in, T_out, C_in, C_out, groups, s);
-    // Measured on the 1-hour shapes (TFLOP/s): 10->14: 4 groups x 128 outputs 73, 2 x 128 72, 2 x 256 67;
-    // 14->18: 2 x 128 75 (31 KB slab, 5 workgroups / CU), 4 x 128 53 (62 KB, 2 / CU), 2 x 256 46.
-    // (De-interleaving the slab into even / odd time steps, which removes the 2-way bank conflict of the
-    //  stride-2 tap reads, changed nothing: the LDS reads are not the limiter.)
-    if (cig == 10 && cog == 14 && groups % 4 == 0)
-        return launch_spec<10, 14, 2, 4, 128, false>(x, wp, bias, 0.f, y, B, T_in, T_out, C_in, C_out, groups, s);
-    if (cig == 14 && cog == 18 && groups % 2 == 0)
-        return launch_spec<14, 18, 2, 2, 128, false>(x, wp, bias, 0.f, y, B, T_in, T_out, C_in, C_out, groups, s);
-    return launch_generic<false>(x, wp, bias, 0.f, y, B, T_in, T_out, C_in, C_out, groups, 2, s);
-}
-
-int launch_gconv_res(const float* x, const float* wp, const float* bias, float alpha, int B, int64_t T, int C,
-                     int groups, float* y, hipStream_t s) {
-    TAL_CHECK_ARG(x && wp && bias && y, "tal_gconv_res_fwd: null pointer");
-    TAL_CHECK_ARG(x != y, "tal_gconv_res_fwd: in-place not supported (halo reads)");
-    TAL_CHECK_ARG(groups > 0 && C % groups == 0, "tal_gconv_res_fwd: C=%d not divisible by groups %d", C, groups);
-    TAL_CHECK_ARG(B > 0 && T > 0, "tal_gconv_res_fwd: bad shape");
-    const int cg = C / groups;
-    // 2 groups x 256 time steps per workgroup (2 waves per group): 22-40 KB slabs, 4+ workgroups
-    // per CU.  Measured on the 1-hour shapes: 66 / 85 / 85 TFLOP/s vs 61 / 67 / 70 with 4 groups.
-    if (cg == 10 && groups % 2 == 0)
-        return launch_spec<10, 10, 1, 2, 256, true>(x, wp, bias, alpha, y, B, T, T, C, C, groups, s);
-    if (cg == 14 && groups % 2 == 0)
-        return launch_spec<14, 14, 1, 2, 256, true>(x, wp, bias, alpha, y, B, T, T, C, C, groups, s);
-    if (cg == 18 && groups % 2 == 0)
-        return launch_spec<18, 18, 1, 2, 256, true>(x, wp, bias, alpha, y, B, T, T, C, C, groups, s);
-    return launch_generic<true>(x, wp, bias, alpha, y, B, T, T, C, C, groups, 1, s);
-}
-
 // ---------------------------------------------------------------------------------------------
 // Grouped convs on the fp16 matrix cores (fp16x3 form, as the dense layers of the block)
 // ---------------------------------------------------------------------------------------------
@@ -364,14 +255,6 @@ typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
 typedef _Float16 f16x8u __attribute__((ext_vector_type(8), aligned(4)));
 typedef _Float16 f16x8a8 __attribute__((ext_vector_type(8), aligned(8)));
-// slab row pitch (halves) of a 10-channel group: 10 = compact (20-byte rows: every fragment read is 4-byte aligned and half
-// of the LDS cycles are bank conflicts), 12 = 24-byte rows (8-byte aligned reads, one more K chunk of 32)
-#ifndef GC_P10
-#define GC_P10 12
-#endif
-#ifndef GC_P18
-#define GC_P18 20
-#endif
 // workgroups per CU the register budget is held to (ablation: GC_LB18 = 3 for the 18-channel stride-1 kernels)
 #ifndef GC_LB18
 #define GC_LB18 2
@@ -380,78 +263,9 @@ typedef _Float16 f16x8a8 __attribute__((ext_vector_type(8), aligned(8)));
 #ifndef GC_PF
 #define GC_PF 2
 #endif
-// K permutation of the fragment reads (GcLayout::PERM); 0: plain order (ablation)
-#ifndef GC_KPERM
-#define GC_KPERM 1
-#endif
 #define GC_LB(CIG, STRIDE) (((CIG) > 16 && (STRIDE) == 1) ? GC_LB18 : 2)
 typedef _Float16 f16x4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-// K-segment layout (host + device, compile time)
-template <int CIG, int STRIDE>
-struct GcLayout {
-    // 18 channels per group, stride 1: one segment of 40-byte rows (GC_P18 = 20: 14 K chunks, 8-byte aligned fragment reads;
-    // -10 % on the kernel alone, -0.5 % on the 1-hour step) or, with GC_P18 = 0, two K segments (16 channels at pitch 16 + 2 at
-    // pitch 8: 17 K chunks, every fragment one aligned 16-byte read -- round 1's form; a 48-byte pitch lost 37 % to bank conflicts)
-    static constexpr bool SPLIT18 = CIG > 16 && STRIDE == 1 && GC_P18 == 0;
-    static constexpr int NSEG = (STRIDE == 2 || SPLIT18) ? 2 : 1;
-    static constexpr int pitch(int s) { return STRIDE == 2 ? 16 : (SPLIT18 ? (s == 0 ? 16 : 8) : (CIG > 16 ? GC_P18 : (CIG == 10 ? GC_P10 : 16))); }
-    static constexpr int ntap(int s) { return STRIDE == 2 ? (s == 0 ? (KS + 1) / 2 : KS / 2) : KS; }
-    static constexpr int nch(int s) { return SPLIT18 ? (s == 0 ? 16 : CIG - 16) : CIG; }
-    static constexpr int choff(int s) { return (SPLIT18 && s == 1) ? 16 : 0; }
-    static constexpr int tap0(int s) { return STRIDE == 2 ? s : 0; }
-    static constexpr int nk(int s) { return s < NSEG ? ((ntap(s) - 1) * pitch(s) + nch(s) + 31) / 32 : 0; }
-    static constexpr int NKS = nk(0) + nk(1);
-    // K permutation against LDS bank conflicts (single-segment stride-1 layouts whose rows are an ODD number of 8-byte bank
-    // pairs apart: 12 or 20 halves).  Lanes 0-31 of a fragment read are 16 output steps x 2 k groups; with the k groups 16
-    // bytes apart every such read is a 2-way conflict (p * d = 4 mod 64 banks has a solution |d| <= 15 for p = 6, 10: SQ_LDS_
-    // BANK_CONFLICT = 48 % of the LDS cycles, the LDS array 70-75 % busy); 128 bytes apart it is conflict-free -- the 16 rows
-    // fill every other bank pair, the second k group the rest.  So inside a block of 128 slab halves (4 K chunks) MFMA j takes
-    // its k groups 0..3 from the 16-byte pieces j, j + 8, j + 4, j + 12; the weights are packed with the same permutation
-    // (pack_gconv_mfma_kernel).  Chunks behind the last whole block of four keep the plain order.
-    static constexpr bool PERM = NSEG == 1 && STRIDE == 1 && pitch(0) % 8 == 4 && GC_KPERM;
-    static constexpr int NKP = PERM ? (nk(0) / 4) * 4 : 0;
-    static constexpr int rows(int s, int tt) { return STRIDE == 2 ? tt + ntap(s) - 1 : tt + KS - 1; }
-    static constexpr int slab(int s, int tt) {       // halves, incl. the K round-up the last output step reads past its window
-        if (s >= NSEG) return 0;
-        const int over = 32 * nk(s) - ntap(s) * pitch(s);
-        return (rows(s, tt) * pitch(s) + (over > 0 ? over : 0) + 7) & ~7;
-    }
-};
-
-// runtime mirror for the weight packer
-struct GcPackDesc {
-    int nseg, pitch[2], ntap[2], nch[2], choff[2], tap0[2], nk[2], tapstep, cig, cog, mt_n, groups;
-    int perm_nk;      // K chunks of segment 0 in the permuted order (GcLayout::PERM)
-};
-template <int CIG, int STRIDE>
-static GcPackDesc make_pack_desc(int cog, int groups) {
-    using LY = GcLayout<CIG, STRIDE>;
-    GcPackDesc d = {};
-    d.nseg = LY::NSEG;
-    for (int s2 = 0; s2 < 2; ++s2) {
-        d.pitch[s2] = LY::pitch(s2); d.ntap[s2] = LY::ntap(s2); d.nch[s2] = LY::nch(s2);
-        d.choff[s2] = LY::choff(s2); d.tap0[s2] = LY::tap0(s2); d.nk[s2] = LY::nk(s2);
-    }
-    d.tapstep = STRIDE; d.cig = CIG; d.cog = cog; d.mt_n = (cog + 15) / 16; d.groups = groups;
-    d.perm_nk = LY::NKP;
-    return d;
-}
-// the (C_in/G, C_out/G, stride) combinations with a kernel; false: none
-static bool gconv_mfma_desc(int cig, int cog, int stride, int groups, GcPackDesc& d) {
-    if (groups <= 0 || groups % 4) return false;
-    if (stride == 1 && cig == cog) {
-        if (cig == 10) { d = make_pack_desc<10, 1>(cog, groups); return true; }
-        if (cig == 14) { d = make_pack_desc<14, 1>(cog, groups); return true; }
-        if (cig == 18) { d = make_pack_desc<18, 1>(cog, groups); return true; }
-    }
-    if (stride == 2) {
-        if (cig == 10 && cog == 14) { d = make_pack_desc<10, 2>(cog, groups); return true; }
-        if (cig == 14 && cog == 18) { d = make_pack_desc<14, 2>(cog, groups); return true; }
-    }
-    return false;
-}
 
 // `p2` = p + 4 halves through a pointer the compiler cannot relate to `p` (8-byte-aligned pitches only): the fragment is then
 // read as TWO ds_read_b64 (2 LDS cycles each).  Left to itself hipcc merges the pair into one ds_read2_b64, which the LDS
@@ -527,9 +341,10 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
                                                            const float* __restrict__ bias, float alpha, float* __restrict__ y,
                                                            _Float16* __restrict__ ysplit, int64_t T_in, int64_t T_out, int C_in,
                                                            int C_out, int* __restrict__ range_flag, int n_tt, int n_gb, const GcC1 c1) {
-    using LY = GcLayout<CIG, STRIDE>;
-    constexpr int NKS = LY::NKS, NK0 = LY::nk(0), MT = (COG + 15) / 16;
-    constexpr int P0 = LY::pitch(0), P1 = LY::pitch(1);
+    constexpr GcLayout LY = gc_layout(CIG, STRIDE);
+    constexpr int NKS = LY.nks(), NK0 = LY.nk[0], MT = (COG + 15) / 16, NSEG = LY.nseg, NCH0 = LY.nch[0], NCH1 = LY.nch[1];
+    constexpr int P0 = LY.pitch[0], P1 = LY.pitch[1];
+    constexpr bool PERM = LY.perm();
     constexpr int PADT = RESID ? KS / 2 : 0;
     // STAGED: the output tile goes through LDS and leaves as 16-byte (8-byte) pieces.  Rows below (tb + 1) * 16 of a group's
     // slab are dead once block tb has its operands, so the block's output halves are written over them (channels 0-15 into
@@ -537,9 +352,9 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
     // (MT == 2) one workgroup barrier per block.  Why: a store instruction costs by the 128-byte lines it touches, not by
     // its bytes -- the direct path (lane = time step) pays 16 lines per instruction, 4-6 instructions per block.
     constexpr bool STAGED = SPLIT == 2 && GB * MT == 4 && (GB * COG) % 4 == 0 && P0 % 4 == 0 && P0 >= (COG < 16 ? 4 * ((COG + 3) / 4) : 16) &&
-                            (MT == 1 || (MT == 2 && ((LY::NSEG == 2 && P1 >= 4) || (LY::NSEG == 1 && P0 >= 4 * ((COG + 3) / 4)))));
+                            (MT == 1 || (MT == 2 && ((NSEG == 2 && P1 >= 4) || (NSEG == 1 && P0 >= 4 * ((COG + 3) / 4)))));
     constexpr int TIN = (TT - 1) * STRIDE + KS;                     // input rows a tile of TT outputs reads
-    constexpr int SL0 = LY::slab(0, TT), SL1 = LY::slab(1, TT), GS = SL0 + SL1;   // halves per group and (hi | lo) array
+    constexpr int SL0 = LY.slab(0, TT), SL1 = LY.slab(1, TT), GS = SL0 + SL1;   // halves per group and (hi | lo) array
     constexpr int CH = GB * CIG, CH4 = CH / 4;
     constexpr int RPP = 256 / CH4;                                  // input rows per pass of the slab load
     static_assert(CH % 4 == 0 && CIG % 2 == 0 && TT % 64 == 0 && (!RESID || (CIG == COG && STRIDE == 1)), "shape");
@@ -555,7 +370,7 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
     GC_STAMP(0);
 
     if constexpr (FROMC1) {
-        static_assert(CIG == 10 && COG == 10 && STRIDE == 1 && RESID && GB == 4 && XSPLIT && SPLIT == 2 && LY::NSEG == 1 && TIN % 4 == 0 && P0 % 2 == 0, "shape");
+        static_assert(CIG == 10 && COG == 10 && STRIDE == 1 && RESID && GB == 4 && XSPLIT && SPLIT == 2 && NSEG == 1 && TIN % 4 == 0 && P0 % 2 == 0, "shape");
         // ---- the slab from the log-mel: stage the tile's mel rows ([row][4 bins], 16-byte loads), then thread = (channel of the
         // workgroup, row phase): a channel's 21 weights + bias in registers, four consecutive rows share their 27 samples ----
         constexpr int NR = 2 * (TIN - 1) + KS;                       // mel rows behind TIN rows of the stage
@@ -627,10 +442,10 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
         }
         note_range(amax, range_flag);
         const f16x2 z2 = {(_Float16)0.f, (_Float16)0.f};
-        constexpr int tail2 = (SL0 - LY::rows(0, TT) * P0) / 2;
+        constexpr int tail2 = (SL0 - LY.rows(0, TT) * P0) / 2;
         if (tail2 > 0)
             for (int i = tid; i < 2 * GB * tail2; i += 256)
-                *reinterpret_cast<f16x2*>(slab + (i / tail2) * GS + LY::rows(0, TT) * P0 + 2 * (i % tail2)) = z2;
+                *reinterpret_cast<f16x2*>(slab + (i / tail2) * GS + LY.rows(0, TT) * P0 + 2 * (i % tail2)) = z2;
     } else
     // ---- slab load: thread = (input row inside a pass, 16-byte column piece): 16-byte global loads (GB*CIG contiguous
     // floats per row), all passes in flight, split, 4-byte LDS stores ----
@@ -643,14 +458,14 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int ch = c4 * 4 + 2 * q, gl = ch / CIG, ci = ch - gl * CIG;
-            const int seg = (STRIDE == 1 && ci >= LY::nch(0)) ? 1 : 0;          // channel split (18 channels per group)
-            so[q] = gl * GS + (seg ? SL0 + ci - LY::nch(0) : ci);
+            const int seg = (STRIDE == 1 && ci >= NCH0) ? 1 : 0;          // channel split (18 channels per group)
+            so[q] = gl * GS + (seg ? SL0 + ci - NCH0 : ci);
             sp[q] = seg ? P1 : P0;
-            const int cis = seg ? ci - LY::nch(0) : ci, nc = LY::nch(seg);
+            const int cis = seg ? ci - NCH0 : ci, nc = seg ? NCH1 : NCH0;
             npad[q] = cis + 2 == nc ? (sp[q] - nc) / 2 : 0;
         }
-        constexpr int MAXPAD = (P0 - LY::nch(0)) / 2 > (LY::NSEG == 2 ? (P1 - LY::nch(1)) / 2 : 0) ? (P0 - LY::nch(0)) / 2
-                                                                                                 : (LY::NSEG == 2 ? (P1 - LY::nch(1)) / 2 : 0);
+        constexpr int MAXPAD = (P0 - NCH0) / 2 > (NSEG == 2 ? (P1 - NCH1) / 2 : 0) ? (P0 - NCH0) / 2
+                                                                                                 : (NSEG == 2 ? (P1 - NCH1) / 2 : 0);
         const unsigned zero_pair = 0u;
         auto pad_row = [&](int q, int off) {          // off: LDS offset (halves) of the pair just stored
 #pragma unroll
@@ -733,8 +548,8 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
         // zeros behind the last row of each segment (the K round-up the last output steps read past their window)
         const f16x2 z2 = {(_Float16)0.f, (_Float16)0.f};
 #pragma unroll
-        for (int sg = 0; sg < LY::NSEG; ++sg) {
-            const int pt = sg ? P1 : P0, rows = LY::rows(sg, TT), sl = sg ? SL1 : SL0, base = sg ? SL0 : 0;
+        for (int sg = 0; sg < NSEG; ++sg) {
+            const int pt = sg ? P1 : P0, rows = sg ? LY.rows(1, TT) : LY.rows(0, TT), sl = sg ? SL1 : SL0, base = sg ? SL0 : 0;
             const int tail2 = (sl - rows * pt) / 2;
             if (tail2 > 0)
                 for (int i = tid; i < 2 * GB * tail2; i += 256)
@@ -773,9 +588,9 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
         asm volatile("" :: "v"(wh[NKS - 1]), "v"(wl[NKS - 1]));
         GC_STAMP(4);
         // fragment of K chunk c for output column (16 tb + col): segment base + (16 tb + col) * pitch + 8 kg + 32 ks
-        // (LY::PERM: k group kg of the chunks below LY::NKP sits 64 (kg & 1) + 32 (kg >> 1) halves into its block of 128)
-        constexpr int NKP = LY::NKP;
-        const int kgo = LY::PERM ? 64 * (kg & 1) + 32 * (kg >> 1) : 8 * kg;
+        // (PERM: k group kg of the chunks below NKP sits 64 (kg & 1) + 32 (kg >> 1) halves into its block of 128)
+        constexpr int NKP = LY.perm_nk;
+        const int kgo = PERM ? 64 * (kg & 1) + 32 * (kg >> 1) : 8 * kg;
         const _Float16* hs = s_hi + gl * GS + kgo;
         const _Float16* ls = s_lo + gl * GS + kgo;
         int four = 4;                        // (opaque to the compiler: hs2 / ls2 become separate base registers, still LDS pointers)
@@ -793,7 +608,7 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
         };
         auto frag = [&](const _Float16* base, int c, int b0, int b1) {
             const bool is_hi = base == hs;
-            const bool plain = LY::PERM && c >= NKP;
+            const bool plain = PERM && c >= NKP;
             const _Float16* b1p = plain ? (is_hi ? hst : lst) : base;
             const _Float16* b2p = plain ? (is_hi ? hst2 : lst2) : (is_hi ? hs2 : ls2);
             return c < NK0 ? gconv_frag<P0>(b1p + frag_off(c, b0, b1), b2p + frag_off(c, b0, b1))
@@ -829,9 +644,9 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
             for (int j = 0; j < XD; ++j) xr[j] = load_x(tbeg + j);
         }
         // XSPLIT: the residual x[t][ch0 .. ch0 + 3] sits in this group's slab (row t - t0 + PADT) as hi / lo halves
-        const int rseg = (STRIDE == 1 && LY::NSEG == 2 && ch0 >= LY::nch(0)) ? 1 : 0;
-        const _Float16* rh = s_hi + gl * GS + (rseg ? SL0 + ch0 - LY::nch(0) : ch0);
-        const _Float16* rl = s_lo + gl * GS + (rseg ? SL0 + ch0 - LY::nch(0) : ch0);
+        const int rseg = (STRIDE == 1 && NSEG == 2 && ch0 >= NCH0) ? 1 : 0;
+        const _Float16* rh = s_hi + gl * GS + (rseg ? SL0 + ch0 - NCH0 : ch0);
+        const _Float16* rl = s_lo + gl * GS + (rseg ? SL0 + ch0 - NCH0 : ch0);
         const int rp = rseg ? P1 : P0;
         constexpr int r01 = 0;
         const int r23 = nvalid >= 4 ? 2 : 0;   // (a lane without valid channels reads initialised slab bytes it never uses)
@@ -919,7 +734,7 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
                             h01p = {hh[0], hh[1]}; l01p = {ll[0], ll[1]}; h23p = {hh[2], hh[3]}; l23p = {ll[2], ll[3]};
                         }
                         typedef _Float16 f16x4a8 __attribute__((ext_vector_type(4), aligned(8)));
-                        const int so2 = gl * GS + ((mt == 0 || LY::NSEG == 1) ? (tb * 16 + col) * P0 + mt * 16 + 4 * kg : SL0 + (tb * 16 + col) * P1 + 4 * kg);
+                        const int so2 = gl * GS + ((mt == 0 || NSEG == 1) ? (tb * 16 + col) * P0 + mt * 16 + 4 * kg : SL0 + (tb * 16 + col) * P1 + 4 * kg);
                         *reinterpret_cast<f16x4a8*>(s_hi + so2) = f16x4a8{h01p[0], h01p[1], h23p[0], h23p[1]};
                         *reinterpret_cast<f16x4a8*>(s_lo + so2) = f16x4a8{l01p[0], l01p[1], l23p[0], l23p[1]};
                     }
@@ -986,7 +801,7 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
 #pragma unroll
         for (int j = 0; j < PW; ++j) {
             const int idx = PW * p + j, gl = idx / WPG, i = idx - gl * WPG;
-            const bool first = i < 8 || (LY::NSEG == 1);      // channels 16, 17 of a two-segment slab sit in segment 1
+            const bool first = i < 8 || (NSEG == 1);      // channels 16, 17 of a two-segment slab sit in segment 1
             wp[j] = first ? P0 : P1;
             wo[j] = (a * GB + gl) * GS + (first ? 2 * i : SL0 + 2 * (i - 8)) + r * wp[j];
         }
@@ -1031,25 +846,21 @@ __global__ __launch_bounds__(256, GC_LB(CIG, STRIDE)) void gconv_mfma_kernel(con
 // An output's chain of MFMAs depends on its shift s = (t - tile start) % 8 only, and tile starts are multiples of 64: long
 // (256) and short (64) tiles give bit-identical results.  Channels 16, 17 differ from gconv_mfma_kernel's in the last bits
 // (other grouping of the products into K chunks), channels 0-15 are the same chains.
-constexpr int S18_NKA = 18;      // K chunks of the shifted tile: (21 + 7) rows x 20 halves = 560 -> 576
-constexpr int S18_SH = 8;        // shifts per channel
 // The shifted tile's A fragments are NOT loaded from memory (18 K chunks x hi / lo x 1 KB per wave, mostly zeros, at the 25-60
 // GB/s a CU pulls from L2: measured 6.8 us of a 22 us workgroup): a group's two left-over channels are 2 x 420 weights; they sit
 // in LDS as a zero-padded line per channel and hi / lo, [S18_WPRE zeros | 420 weights in slab order tap * 20 + channel | zeros],
-// and row (c, s), k group kg of chunk ch is the 8 halves at S18_WPRE + 32 ch + 8 kg - 20 s of line c.
-constexpr int S18_WPRE = 20 * (S18_SH - 1);                   // 140
-constexpr int S18_WL = S18_WPRE + 32 * S18_NKA + 8;           // 724 halves per line, rounded up so that a workgroup's eight lines are
-constexpr int S18_WLP = (S18_WL + 255) & ~255;                // a whole number of 256 x 16-byte pieces (768)
+// and row (c, s), k group kg of chunk ch is the 8 halves at S18_WPRE + 32 ch + 8 kg - 20 s of line c.  (S18_NKA = 18 K chunks,
+// S18_SH = 8 shifts, S18_WPRE, S18_WL and the padded line length S18_WLP: csrc/gconv_plan.h, the host sizes LDS and the table by them.)
 
 template <int TT>
 __global__ __launch_bounds__(256, 2) void gconv18_shift_kernel(const float* __restrict__ x, const _Float16* __restrict__ wfrag,
                                                              const _Float16* __restrict__ wshift, const float* __restrict__ bias, float alpha,
                                                              _Float16* __restrict__ ysplit, int64_t T, int C, int* __restrict__ range_flag,
                                                              int n_tt, int n_gb, int nb_total) {
-    using LY = GcLayout<18, 1>;
-    static_assert(LY::NSEG == 1 && LY::pitch(0) == 20 && LY::PERM && LY::nk(0) == 14, "the shift-packed kernel is built for 40-byte slab rows");
-    constexpr int CG = 18, GB = 2, P = 20, NK = 14, NKP = LY::NKP, PADT = KS / 2;
-    constexpr int TIN = TT + KS - 1, GS = LY::slab(0, TT);
+    constexpr GcLayout LY = gc_layout(18, 1);
+    static_assert(LY.nseg == 1 && LY.pitch[0] == 20 && LY.perm() && LY.nk[0] == 14, "the shift-packed kernel is built for 40-byte slab rows");
+    constexpr int CG = 18, GB = 2, P = 20, NK = 14, NKP = LY.perm_nk, PADT = KS / 2;
+    constexpr int TIN = TT + KS - 1, GS = LY.slab(0, TT);
     static_assert(GS * 2 >= ((TT >= 128 ? TT - 8 : TT - 8) * P + 32 * S18_NKA) * 2, "slab tail");
     constexpr int CH = GB * CG, CH4 = CH / 4, RPP = 256 / CH4;
     extern __shared__ __attribute__((aligned(16))) _Float16 slab[];   // [2 (hi, lo)][GB][GS] | weight lines [GB][2 (channel)][2 (hi, lo)][S18_WLP]
@@ -1404,7 +1215,7 @@ __global__ void pack_gconv_shift18_kernel(const float* __restrict__ src, _Float1
 // reference Conv1d weight [C_out, C_in/G, 21] -> MFMA A fragments [g][mt][K chunk][hi, lo][lane][8 halves]:
 // row = mt * 16 + (lane & 15) (output channel); chunk c of segment s, k = 32 ks + 8 (lane >> 4) + i = j * pitch + cc
 // -> tap tap0 + j * stride, input channel choff + cc
-__global__ void pack_gconv_mfma_kernel(const float* __restrict__ src, _Float16* __restrict__ dst, const GcPackDesc d) {
+__global__ void pack_gconv_mfma_kernel(const float* __restrict__ src, _Float16* __restrict__ dst, const GcLayout d) {
     const int nks = d.nk[0] + d.nk[1];
     const int64_t total = (int64_t)d.groups * d.mt_n * nks * 64 * 8;
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1429,211 +1240,217 @@ __global__ void pack_gconv_mfma_kernel(const float* __restrict__ src, _Float16* 
     dst[base + 64 * 8] = lo;
 }
 
-// (the split-input slab load moves 4-channel pieces that must not straddle a 32-channel block: the workgroup's first channel,
-//  g0 * CIG with g0 a multiple of GB, has to be a multiple of 4)
-template <int CIG, int GB>
-static constexpr bool g0_aligned() { return (CIG * GB) % 4 == 0; }
+// ---------------------------------------------------------------------------------------------
+// Host side.  Every decision is gconv_plan's (csrc/gconv_plan.h): a launcher checks its pointers, states the call, and
+// launch_planned maps the plan to the instantiation.
+// ---------------------------------------------------------------------------------------------
+static_assert(GCP_RES == PROF_GCONV_RES && GCP_S2 == PROF_GCONV_S2, "the plan names the profiling scopes by their ProfClass values");
 
-// grid of the matrix-core kernels: 1-D in the XCD-aware order (GC_BLOCK_INDEX) unless it would not fit 32 bits or the plain
-// grid is asked for
-static dim3 gconv_grid(int64_t tiles, int group_blocks, int B, int& n_tt, int& n_gb) {
-    const int64_t nb = tiles * group_blocks * B;
-    if (nb < (1ll << 31) && tiles < (1ll << 31) && !opt(OPT_GCONV_GRID_XYZ)) {
-        n_tt = (int)tiles;
-        n_gb = group_blocks;
-        return dim3((unsigned)nb);
-    }
-    n_tt = n_gb = 0;
-    return dim3((unsigned)tiles, (unsigned)group_blocks, (unsigned)B);
+// a refused plan: its message (also for the entries of gconv_general.hip)
+int gconv_refused(const GconvCall& c, int why) {
+    char text[160];
+    gconv_refusal_text(c, why, text, sizeof text);
+    set_error("%s", text);
+    return TAL_EINVAL;
 }
 
-// x_split: the input is in the split form; y == NULL with ysplit: only the split form of the output is written
+GconvCall gconv_call(int entry, int B, int64_t T_in, int C_in, int C_out, int groups, int ks, const void* x) {
+    GconvCall c = {};
+    c.entry = entry; c.B = B; c.T_in = T_in; c.C_in = C_in; c.C_out = C_out; c.groups = groups; c.ks = ks;
+    c.x_lo = (unsigned)(reinterpret_cast<uintptr_t>(x) & 15);
+    c.cus = device_cus();
+    c.o.c1_generic = opt(OPT_GCONV_C1_GENERIC);
+    c.o.short_below = opt(OPT_GCONV_SHORT_BELOW);
+    c.o.no_shift18 = opt(OPT_GCONV_NO_SHIFT18);
+    c.o.grid_xyz = opt(OPT_GCONV_GRID_XYZ);
+    c.o.long_tt = opt(OPT_GCONV_LONG_TT);
+    return c;
+}
+
+bool gconv_s2_can_split(int C_in, int C_out, int groups, const float* x) {
+    return gconv_c1_ok(C_in, C_out, groups, (unsigned)(reinterpret_cast<uintptr_t>(x) & 15), opt(OPT_GCONV_C1_GENERIC) != 0, true, false);
+}
+// the shapes whose first resize conv can take the mean of its input as a bias correction (gconv_s2_c1_kernel)
+bool gconv_s2_can_fold_mean(int C_in, int C_out, int groups, const float* x) {
+    return gconv_c1_ok(C_in, C_out, groups, (unsigned)(reinterpret_cast<uintptr_t>(x) & 15), opt(OPT_GCONV_C1_GENERIC) != 0, false, true);
+}
+
+bool gconv_c1_res_fusable(int C_in, int C_out, int groups, const float* mel) {
+    return gconv_c1_res_fusable(C_in, C_out, groups, (unsigned)(reinterpret_cast<uintptr_t>(mel) & 15));
+}
+
+namespace {
+
+// what the kernels of this file take besides the plan's geometry
+struct GconvArgs {
+    const float* x;
+    const void* w;          // packed fp32 weights, or the fragment table
+    const float* bias;
+    float alpha;
+    float* y;
+    void* y_split;
+    int* range_flag;
+    const float* in_mean;
+    int64_t T_in;           // rows of the conv's input
+    int C_in, C_out, groups;
+    GcC1 c1;
+};
+
+// the instantiations, each list written once: (CIG, COG, STRIDE, GB, TT, RESID) of gconv_kernel ...
+#define GCONV_VALU_SPECS(X) \
+    X(1, 10, 2, 16, 128, false) X(10, 14, 2, 4, 128, false) X(14, 18, 2, 2, 128, false) X(10, 10, 1, 2, 256, true) X(14, 14, 1, 2, 256, true) X(18, 18, 1, 2, 256, true)
+// ... and (CIG, COG, STRIDE, RESID, GB, TT) of gconv_mfma_kernel, each in its six SPLIT x XSPLIT variants
+#define GCONV_MFMA_SPECS(X)                                                                                                     \
+    X(10, 10, 1, true, 4, 64) X(14, 14, 1, true, 4, 64) X(18, 18, 1, true, 2, 64) X(10, 10, 1, true, 4, 128) X(14, 14, 1, true, 4, 128) \
+    X(10, 10, 1, true, 4, 256) X(14, 14, 1, true, 4, 256) X(18, 18, 1, true, 2, 256)                                             \
+    X(10, 14, 2, false, 4, 64) X(14, 18, 2, false, 2, 64) X(10, 14, 2, false, 4, 128) X(14, 18, 2, false, 2, 128)
+
 template <int CIG, int COG, int STRIDE, bool RESID, int GB, int TT>
-static int launch_mfma_spec(const float* x, const void* wfrag, const float* bias, float alpha, float* y, void* ysplit, int B,
-                            int64_t T_in, int64_t T_out, int C_in, int C_out, int groups, hipStream_t s, int* range_flag,
-                            bool x_split = false) {
-    using LY = GcLayout<CIG, STRIDE>;
-    constexpr size_t lds = (size_t)2 * GB * (LY::slab(0, TT) + LY::slab(1, TT)) * sizeof(_Float16);
-    typedef void (*kern_t)(const float*, const _Float16*, const float*, float, float*, _Float16*, int64_t, int64_t, int, int, int*, int, int, const GcC1);
-    kern_t k;
-    if (x_split) k = y ? (ysplit ? (kern_t)gconv_mfma_kernel<CIG, COG, STRIDE, RESID, GB, TT, 1, true> : (kern_t)gconv_mfma_kernel<CIG, COG, STRIDE, RESID, GB, TT, 0, true>)
-                       : (kern_t)gconv_mfma_kernel<CIG, COG, STRIDE, RESID, GB, TT, 2, true>;
-    else k = y ? (ysplit ? (kern_t)gconv_mfma_kernel<CIG, COG, STRIDE, RESID, GB, TT, 1, false> : (kern_t)gconv_mfma_kernel<CIG, COG, STRIDE, RESID, GB, TT, 0, false>)
-               : (kern_t)gconv_mfma_kernel<CIG, COG, STRIDE, RESID, GB, TT, 2, false>;
-    TAL_CHECK_ARG(y || ysplit, "gconv (fp16x3): no output buffer");
-    TAL_CHECK_ARG(!ysplit || C_out % 32 == 0, "gconv (fp16x3): the split output needs C_out %% 32 == 0");
-    TAL_CHECK_ARG(!x_split || (C_in % 32 == 0 && (g0_aligned<CIG, GB>())), "gconv (fp16x3): the split input needs C_in %% 32 == 0");
-    static const void* attr_done[6] = {};          // (one slot per variant of this instantiation)
-    const int slot = (x_split ? 3 : 0) + (y ? (ysplit ? 1 : 0) : 2);
-    if (attr_done[slot] != reinterpret_cast<const void*>(k)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            set_error("gconv (fp16x3): cannot reserve %zu bytes of LDS", lds);
-            return TAL_EHIP;
+int launch_mfma_spec(const GconvLaunch& p, dim3 grid, const GconvArgs& a, hipStream_t s) {
+    auto go = [&](auto split, auto xsplit) {
+        return gconv_launch_planned<gconv_mfma_kernel<CIG, COG, STRIDE, RESID, GB, TT, decltype(split)::value, decltype(xsplit)::value>>(
+            p, grid, "gconv (fp16x3)", s, a.x, reinterpret_cast<const _Float16*>(a.w), a.bias, a.alpha, a.y, reinterpret_cast<_Float16*>(a.y_split),
+            a.T_in, p.T_out, a.C_in, a.C_out, a.range_flag, p.n_tt, p.n_gb, GcC1{});
+    };
+    using std::integral_constant;
+    using std::false_type;
+    using std::true_type;
+    if (p.xsplit) return p.split == 0 ? go(integral_constant<int, 0>(), true_type()) : p.split == 1 ? go(integral_constant<int, 1>(), true_type()) : go(integral_constant<int, 2>(), true_type());
+    return p.split == 0 ? go(integral_constant<int, 0>(), false_type()) : p.split == 1 ? go(integral_constant<int, 1>(), false_type()) : go(integral_constant<int, 2>(), false_type());
+}
+
+int launch_planned(const GconvCall& c, const GconvArgs& a, hipStream_t s) {
+    const GconvLaunch p = gconv_plan(c);
+    if (p.refusal) return gconv_refused(c, p.refusal);
+    if (p.grid_x == 0) return TAL_OK;
+    dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+    const float* wp = reinterpret_cast<const float*>(a.w);
+    const _Float16* wfrag = reinterpret_cast<const _Float16*>(a.w);
+    switch (p.kernel) {
+        case GCK_VALU_TILED:
+#define X(CIG, COG, STRIDE, GB, TT, RESID)                                                                                           \
+    if (p.cig == CIG && p.cog == COG && p.stride == STRIDE && p.gb == GB && p.tt == TT && p.resid == RESID)                          \
+        return gconv_launch_planned<gconv_kernel<CIG, COG, STRIDE, GB, TT, RESID>>(p, grid, "gconv", s, a.x, wp, a.bias, a.alpha, a.y, a.T_in, \
+                                                                                   p.T_out, a.C_in, a.C_out);
+            GCONV_VALU_SPECS(X)
+#undef X
+            break;
+        case GCK_VALU_GENERIC: {
+            const int64_t total = (int64_t)c.B * p.T_out * a.C_out;
+            if (p.resid) return gconv_launch_planned<gconv_generic_kernel<true>>(p, grid, "gconv_generic", s, a.x, wp, a.bias, a.alpha, a.y, a.T_in, p.T_out, a.C_in, a.C_out, p.cig, p.cog, p.stride, total);
+            return gconv_launch_planned<gconv_generic_kernel<false>>(p, grid, "gconv_generic", s, a.x, wp, a.bias, a.alpha, a.y, a.T_in, p.T_out, a.C_in, a.C_out, p.cig, p.cog, p.stride, total);
         }
-        attr_done[slot] = reinterpret_cast<const void*>(k);
+        case GCK_C1: {
+            float* yo = a.y_split ? reinterpret_cast<float*>(a.y_split) : a.y;
+#define X(TT, YSPLIT)                                                                                                                          \
+    if (p.tt == TT && p.ysplit == YSPLIT)                                                                                                      \
+        return gconv_launch_planned<gconv_s2_c1_kernel<10, 20, TT, YSPLIT>>(p, grid, "gconv (1 channel per group)", s, a.x, wp, a.bias, yo, a.T_in, \
+                                                                            p.T_out, a.C_in, a.C_out, a.range_flag, a.in_mean);
+            X(32, true) X(256, true) X(32, false) X(256, false)
+#undef X
+            break;
+        }
+        case GCK_MFMA:
+#define X(CIG, COG, STRIDE, RESID, GB, TT) \
+    if (p.cig == CIG && p.cog == COG && p.stride == STRIDE && p.gb == GB && p.tt == TT) return launch_mfma_spec<CIG, COG, STRIDE, RESID, GB, TT>(p, grid, a, s);
+            GCONV_MFMA_SPECS(X)
+#undef X
+            break;
+        case GCK_SHIFT18: {
+            // the weight lines of channels 16, 17 sit behind the fragment table
+            const _Float16* wshift = wfrag + gc_layout(18, 1, 18, a.groups).main_halves();
+#ifdef GC_S18_PERSIST
+            if (p.n_tt > 0 && grid.x > 2u * (unsigned)device_cus()) grid = dim3(2u * (unsigned)device_cus());
+#endif
+            if (p.tt == 64)
+                return gconv_launch_planned<gconv18_shift_kernel<64>>(p, grid, "gconv (fp16x3, shifted tile)", s, a.x, wfrag, wshift, a.bias, a.alpha,
+                                                                      reinterpret_cast<_Float16*>(a.y_split), a.T_in, a.C_out, a.range_flag, p.n_tt, p.n_gb, p.nb_total);
+            return gconv_launch_planned<gconv18_shift_kernel<256>>(p, grid, "gconv (fp16x3, shifted tile)", s, a.x, wfrag, wshift, a.bias, a.alpha,
+                                                                   reinterpret_cast<_Float16*>(a.y_split), a.T_in, a.C_out, a.range_flag, p.n_tt, p.n_gb, p.nb_total);
+        }
+        case GCK_C1_RES:
+#define X(TT)                                                                                                                                              \
+    if (p.tt == TT)                                                                                                                                        \
+        return gconv_launch_planned<gconv_mfma_kernel<10, 10, 1, true, 4, TT, 2, true, true>>(p, grid, "gconv (resize conv + TDSBlock conv)", s, (const float*)nullptr, \
+                                                                                              wfrag, a.bias, a.alpha, (float*)nullptr, reinterpret_cast<_Float16*>(a.y_split), \
+                                                                                              p.T_out, p.T_out, a.C_out, a.C_out, a.range_flag, p.n_tt, p.n_gb, a.c1);
+            X(64) X(256)
+#undef X
+            break;
+        default: break;
     }
-    int n_tt, n_gb;
-    const dim3 grid = gconv_grid(cdiv(T_out, TT), groups / GB, B, n_tt, n_gb);
-    ProfScope prof(RESID ? PROF_GCONV_RES : PROF_GCONV_S2, 2.0 * (double)B * (double)T_out * C_out * CIG * KS, s);
-    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, x, reinterpret_cast<const _Float16*>(wfrag), bias, alpha, y,
-                       reinterpret_cast<_Float16*>(ysplit), T_in, T_out, C_in, C_out, range_flag, n_tt, n_gb, GcC1{});
-    TAL_CHECK_LAUNCH("gconv (fp16x3)");
-    return TAL_OK;
+    set_error("gconv: the plan names a kernel that is not built (family %d, %d -> %d channels per group, stride %d, %d groups x %d steps)", p.kernel, p.cig,
+              p.cog, p.stride, p.gb, p.tt);
+    return TAL_EINVAL;
 }
 
-// Short inputs: tiles of 64 output steps instead of 256 (128 for stride 2) when the long tiles would not give every CU
-// gconv_short_below workgroups (option "gconv_short_below", default 4: two rounds of two resident workgroups) -- a wave then
-// walks 4 blocks of 16 steps instead of 16 behind its slab fill, on 4x the workgroups.  Same arithmetic per output: results
-// do not depend on the tile length.
-static bool gconv_short_tiles(int64_t T_out, int tt_long, int group_blocks, int B) {
-    return cdiv(T_out, tt_long) * group_blocks * B < (int64_t)opt(OPT_GCONV_SHORT_BELOW) * device_cus();
+}  // namespace
+
+int launch_gconv_s2(const float* x, const float* wp, const float* bias, int B, int64_t T_in, int C_in, int C_out,
+                    int groups, float* y, hipStream_t s, void* y_split, int* range_flag, const float* in_mean) {
+    TAL_CHECK_ARG(x && wp && bias && (y || y_split), "tal_gconv_s2_fwd: null pointer");
+    GconvCall c = gconv_call(GE_S2, B, T_in, C_in, C_out, groups, KS, x);
+    c.has_y = y != nullptr; c.has_y_split = y_split != nullptr; c.has_in_mean = in_mean != nullptr;
+    GconvArgs a = {x, wp, bias, 0.f, y, y_split, range_flag, in_mean, T_in, C_in, C_out, groups, {}};
+    return launch_planned(c, a, s);
 }
 
-// the slab loads address one batch item ([T, C] floats) through a buffer descriptor with 32-bit byte offsets
-bool gconv_f16x3_fits(int64_t T, int C) { return T * C * 4 + (int64_t)300 * C * 4 < ((int64_t)1 << 31); }
-
-// halves of the [g][mt][K chunk][hi, lo][lane][8] fragment table; the 18-channel stride-1 conv keeps a second table behind it:
-// the weight lines of its two left-over channels (gconv18_shift_kernel, pack_gconv_shift18_kernel)
-static size_t gconv_f16x3_main_halves(const GcPackDesc& d) { return (size_t)d.groups * d.mt_n * (d.nk[0] + d.nk[1]) * 2 * 64 * 8; }
-static bool gconv_has_shift18(const GcPackDesc& d) { return d.cig == 18 && d.cog == 18 && d.tapstep == 1 && d.nseg == 1 && d.pitch[0] == 20; }
-
-size_t gconv_f16x3_weight_bytes(int C_in, int C_out, int groups, int stride) {
-    if (groups <= 0 || C_in % groups || C_out % groups) return 0;
-    GcPackDesc d;
-    if (!gconv_mfma_desc(C_in / groups, C_out / groups, stride, groups, d)) return 0;
-    return gconv_f16x3_main_halves(d) * sizeof(_Float16) + (gconv_has_shift18(d) ? (size_t)groups * 4 * S18_WLP * sizeof(_Float16) : 0);
+int launch_gconv_res(const float* x, const float* wp, const float* bias, float alpha, int B, int64_t T, int C,
+                     int groups, float* y, hipStream_t s) {
+    TAL_CHECK_ARG(x && wp && bias && y, "tal_gconv_res_fwd: null pointer");
+    TAL_CHECK_ARG(x != y, "tal_gconv_res_fwd: in-place not supported (halo reads)");
+    GconvCall c = gconv_call(GE_RES, B, T, C, C, groups, KS, x);
+    c.has_y = true;
+    GconvArgs a = {x, wp, bias, alpha, y, nullptr, nullptr, nullptr, T, C, C, groups, {}};
+    return launch_planned(c, a, s);
 }
+
+size_t gconv_f16x3_weight_bytes(int C_in, int C_out, int groups, int stride) { return gconv_weight_table_bytes(C_in, C_out, groups, stride); }
 
 int launch_pack_gconv_f16x3(const float* w_ref, void* w_frag, int C_in, int C_out, int groups, int stride, hipStream_t s) {
     TAL_CHECK_ARG(w_ref && w_frag, "tal_pack_gconv_f16x3_weight: null pointer");
-    GcPackDesc d;
-    TAL_CHECK_ARG(groups > 0 && C_in % groups == 0 && C_out % groups == 0 && gconv_mfma_desc(C_in / groups, C_out / groups, stride, groups, d),
+    TAL_CHECK_ARG(gconv_has_mfma(C_in, C_out, groups, stride),
                   "tal_pack_gconv_f16x3_weight: no fp16x3 kernel for %d -> %d channels, groups=%d, stride %d", C_in, C_out, groups, stride);
-    const int64_t total = (int64_t)groups * d.mt_n * (d.nk[0] + d.nk[1]) * 64 * 8;
+    const GcLayout d = gc_layout(C_in / groups, stride, C_out / groups, groups);
+    const int64_t total = (int64_t)(d.main_halves() / 2);
     hipLaunchKernelGGL(pack_gconv_mfma_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, w_ref, reinterpret_cast<_Float16*>(w_frag), d);
     TAL_CHECK_LAUNCH("tal_pack_gconv_f16x3_weight");
-    if (gconv_has_shift18(d)) {
+    if (d.has_shift18()) {
         const int64_t ts = (int64_t)groups * 2 * S18_WLP;
         hipLaunchKernelGGL(pack_gconv_shift18_kernel, dim3((unsigned)cdiv(ts, 256)), dim3(256), 0, s, w_ref,
-                           reinterpret_cast<_Float16*>(w_frag) + gconv_f16x3_main_halves(d), groups);
+                           reinterpret_cast<_Float16*>(w_frag) + d.main_halves(), groups);
         TAL_CHECK_LAUNCH("tal_pack_gconv_f16x3_weight (shifted tile)");
     }
     return TAL_OK;
 }
 
-// The first resize conv (1 mel bin -> 10 channels per group) and the first TDSBlock conv of the stage as ONE launch (FROMC1):
-// mel [B][T_mel][groups] -> y_split [B][T1][10 groups] in the split form, T1 = (T_mel - 21) / 2 + 1.
-bool gconv_c1_res_fusable(int C_in, int C_out, int groups, const float* mel) {
-    return groups > 0 && C_in == groups && C_out == 10 * groups && groups % 4 == 0 && C_out % 32 == 0 &&
-           (reinterpret_cast<uintptr_t>(mel) & 15) == 0 && gconv_f16x3_weight_bytes(C_out, C_out, groups, 1) > 0;
-}
-template <int TT>
-static int launch_c1_res_tt(const GcC1& c1, const void* wfrag, const float* bias, float alpha, int B, int64_t T1, int C, int groups,
-                            void* ysplit, hipStream_t s, int* range_flag) {
-    using LY = GcLayout<10, 1>;
-    constexpr int GB = 4, TIN = TT + KS - 1, NR = 2 * (TIN - 1) + KS;
-    constexpr size_t lds = (size_t)2 * GB * LY::slab(0, TT) * sizeof(_Float16) + (size_t)NR * GB * sizeof(float);
-    auto k = gconv_mfma_kernel<10, 10, 1, true, GB, TT, 2, true, true>;
-    static const void* attr_done = nullptr;
-    if (attr_done != reinterpret_cast<const void*>(k)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            set_error("gconv (resize conv + TDSBlock conv): cannot reserve %zu bytes of LDS", lds);
-            return TAL_EHIP;
-        }
-        attr_done = reinterpret_cast<const void*>(k);
-    }
-    int n_tt, n_gb;
-    const dim3 grid = gconv_grid(cdiv(T1, TT), groups / GB, B, n_tt, n_gb);
-    ProfScope prof(PROF_GCONV_RES, 2.0 * (double)B * (double)T1 * C * (10 + 1) * KS, s);
-    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, (const float*)nullptr, reinterpret_cast<const _Float16*>(wfrag), bias, alpha, (float*)nullptr,
-                       reinterpret_cast<_Float16*>(ysplit), T1, T1, C, C, range_flag, n_tt, n_gb, c1);
-    TAL_CHECK_LAUNCH("gconv (resize conv + TDSBlock conv)");
-    return TAL_OK;
-}
 int launch_gconv_c1_res_f16x3(const float* mel, const float* w1, const float* b1, const float* in_mean, const void* w_frag, const float* bias,
                               float alpha, int B, int64_t T_mel, int groups, void* y_split, hipStream_t s, int* range_flag) {
     TAL_CHECK_ARG(mel && w1 && b1 && w_frag && bias && y_split, "gconv (resize conv + TDSBlock conv): null pointer");
-    TAL_CHECK_ARG(B > 0 && T_mel >= KS && gconv_c1_res_fusable(groups, 10 * groups, groups, mel), "gconv (resize conv + TDSBlock conv): shape not supported");
-    const int64_t T1 = (T_mel - KS) / 2 + 1;
-    const int C = 10 * groups;
-    TAL_CHECK_ARG(gconv_f16x3_fits(T1, C), "gconv (resize conv + TDSBlock conv): one batch item must stay below 2 GiB");
-    GcC1 c1 = {mel, w1, b1, in_mean, T_mel, groups};
-    if (gconv_short_tiles(T1, 256, groups / 4, B)) return launch_c1_res_tt<64>(c1, w_frag, bias, alpha, B, T1, C, groups, y_split, s, range_flag);
-    return launch_c1_res_tt<256>(c1, w_frag, bias, alpha, B, T1, C, groups, y_split, s, range_flag);
+    GconvCall c = gconv_call(GE_C1_RES, B, T_mel, groups, 10 * groups, groups, KS, mel);
+    c.x_split = c.has_y_split = true;
+    GconvArgs a = {nullptr, w_frag, bias, alpha, nullptr, y_split, range_flag, nullptr, 0, 0, 10 * groups, groups, {mel, w1, b1, in_mean, T_mel, groups}};
+    return launch_planned(c, a, s);
 }
 
+// x_split: x is in the hi / lo split form; y == NULL: only the split form of the output (y_split) is written
 int launch_gconv_res_f16x3(const float* x, const void* w_frag, const float* bias, float alpha, int B, int64_t T, int C, int groups,
                            float* y, void* y_split, hipStream_t s, int* range_flag, bool x_split) {
     TAL_CHECK_ARG(x && w_frag && bias && (y || y_split), "tal_gconv_res_f16x3_fwd: null pointer");
     TAL_CHECK_ARG((const void*)x != (const void*)y && (const void*)x != y_split, "tal_gconv_res_f16x3_fwd: in-place not supported (halo reads)");
-    TAL_CHECK_ARG(gconv_f16x3_weight_bytes(C, C, groups, 1) > 0, "tal_gconv_res_f16x3_fwd: no fp16x3 kernel for C=%d groups=%d", C, groups);
-    TAL_CHECK_ARG(B > 0 && T > 0, "tal_gconv_res_f16x3_fwd: bad shape");
-    TAL_CHECK_ARG(!y_split || C % 32 == 0, "tal_gconv_res_f16x3_fwd: the split output needs C %% 32 == 0 (C=%d)", C);
-    TAL_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0 && C % 4 == 0, "tal_gconv_res_f16x3_fwd: x must be 16-byte aligned");
-    TAL_CHECK_ARG(gconv_f16x3_fits(T, C), "tal_gconv_res_f16x3_fwd: one batch item must stay below 2 GiB (T=%lld, C=%d)", (long long)T, C);
-    const int cg = C / groups;
-    if (cg == 18 && x_split && !y && y_split && GC_P18 == 20 && GC_KPERM && !opt(OPT_GCONV_NO_SHIFT18)) {
-        // the product path of the last stage: split form in and out -> the time-shift-packed kernel
-        GcPackDesc d;
-        gconv_mfma_desc(18, 18, 1, groups, d);
-        const _Float16* wshift = reinterpret_cast<const _Float16*>(w_frag) + gconv_f16x3_main_halves(d);
-        const bool shortt = gconv_short_tiles(T, 256, groups / 2, B);
-        using LY = GcLayout<18, 1>;
-        const size_t lds = ((size_t)2 * 2 * LY::slab(0, shortt ? 64 : 256) + (size_t)2 * 4 * S18_WLP) * sizeof(_Float16);
-        auto kern = shortt ? gconv18_shift_kernel<64> : gconv18_shift_kernel<256>;
-        static const void* attr_done[2] = {};
-        if (attr_done[shortt] != reinterpret_cast<const void*>(kern)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                set_error("gconv (fp16x3, shifted tile): cannot reserve %zu bytes of LDS", lds);
-                return TAL_EHIP;
-            }
-            attr_done[shortt] = reinterpret_cast<const void*>(kern);
-        }
-        int n_tt, n_gb;
-        dim3 grid = gconv_grid(cdiv(T, shortt ? 64 : 256), groups / 2, B, n_tt, n_gb);
-        const int nb_total = n_tt > 0 ? (int)grid.x : 0;
-#ifdef GC_S18_PERSIST
-        if (n_tt > 0 && grid.x > 2u * (unsigned)device_cus()) grid = dim3(2u * (unsigned)device_cus());
-#endif
-        ProfScope prof(PROF_GCONV_RES, 2.0 * (double)B * (double)T * C * cg * KS, s);
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, x, reinterpret_cast<const _Float16*>(w_frag), wshift, bias, alpha,
-                           reinterpret_cast<_Float16*>(y_split), T, C, range_flag, n_tt, n_gb, nb_total);
-        TAL_CHECK_LAUNCH("gconv (fp16x3, shifted tile)");
-        return TAL_OK;
-    }
-    if (gconv_short_tiles(T, 256, groups / (cg == 18 ? 2 : 4), B)) {
-        if (cg == 10) return launch_mfma_spec<10, 10, 1, true, 4, 64>(x, w_frag, bias, alpha, y, y_split, B, T, T, C, C, groups, s, range_flag, x_split);
-        if (cg == 14) return launch_mfma_spec<14, 14, 1, true, 4, 64>(x, w_frag, bias, alpha, y, y_split, B, T, T, C, C, groups, s, range_flag, x_split);
-        return launch_mfma_spec<18, 18, 1, true, 2, 64>(x, w_frag, bias, alpha, y, y_split, B, T, T, C, C, groups, s, range_flag, x_split);
-    }
-    // Long inputs, 14 channels per group: 128-step tiles (38 KB of LDS: four workgroups per CU instead of two at 71 KB) -- the halo grows
-    // from 8 to 16 % of the rows filled, but twice the workgroups overlap their dependent phases: 0.317 -> 0.298 ms on the 1-hour shape,
-    // 0.220 -> 0.200 on eight 5-minute segments (profiles/r6_gconv_tile_lengths.txt).  10 channels per group (53 KB: three per CU
-    // already) lose 9 % with 128 steps and stay at 256; 64-step tiles lose everywhere on long inputs.  Same chain of MFMAs per output:
-    // results do not depend on the tile length.  Option gconv_long_tt: 256 / 128 force one length for both widths.
-    const int long_tt = opt(OPT_GCONV_LONG_TT);
-    if (long_tt == 128 && cg == 10) return launch_mfma_spec<10, 10, 1, true, 4, 128>(x, w_frag, bias, alpha, y, y_split, B, T, T, C, C, groups, s, range_flag, x_split);
-    if (long_tt != 256 && cg == 14) return launch_mfma_spec<14, 14, 1, true, 4, 128>(x, w_frag, bias, alpha, y, y_split, B, T, T, C, C, groups, s, range_flag, x_split);
-    if (cg == 10) return launch_mfma_spec<10, 10, 1, true, 4, 256>(x, w_frag, bias, alpha, y, y_split, B, T, T, C, C, groups, s, range_flag, x_split);
-    if (cg == 14) return launch_mfma_spec<14, 14, 1, true, 4, 256>(x, w_frag, bias, alpha, y, y_split, B, T, T, C, C, groups, s, range_flag, x_split);
-    return launch_mfma_spec<18, 18, 1, true, 2, 256>(x, w_frag, bias, alpha, y, y_split, B, T, T, C, C, groups, s, range_flag, x_split);
+    GconvCall c = gconv_call(GE_RES_F16X3, B, T, C, C, groups, KS, x);
+    c.x_split = x_split; c.has_y = y != nullptr; c.has_y_split = y_split != nullptr;
+    GconvArgs a = {x, w_frag, bias, alpha, y, y_split, range_flag, nullptr, T, C, C, groups, {}};
+    return launch_planned(c, a, s);
 }
 
 int launch_gconv_s2_f16x3(const float* x, const void* w_frag, const float* bias, int B, int64_t T_in, int C_in, int C_out, int groups,
                           float* y, hipStream_t s, int* range_flag, bool x_split, void* y_split) {
     TAL_CHECK_ARG(x && w_frag && bias && (y || y_split), "tal_gconv_s2_f16x3_fwd: null pointer");
-    TAL_CHECK_ARG(gconv_f16x3_weight_bytes(C_in, C_out, groups, 2) > 0, "tal_gconv_s2_f16x3_fwd: no fp16x3 kernel for %d -> %d channels, groups=%d",
-                  C_in, C_out, groups);
-    TAL_CHECK_ARG(B > 0 && T_in >= KS, "tal_gconv_s2_f16x3_fwd: T_in=%lld shorter than the kernel", (long long)T_in);
-    TAL_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0 && C_in % 4 == 0, "tal_gconv_s2_f16x3_fwd: x must be 16-byte aligned");
-    TAL_CHECK_ARG(gconv_f16x3_fits(T_in, C_in), "tal_gconv_s2_f16x3_fwd: one batch item must stay below 2 GiB (T=%lld, C=%d)", (long long)T_in, C_in);
-    const int64_t T_out = (T_in - KS) / 2 + 1;
-    if (gconv_short_tiles(T_out, 128, groups / (C_in / groups == 10 ? 4 : 2), B)) {
-        if (C_in / groups == 10) return launch_mfma_spec<10, 14, 2, false, 4, 64>(x, w_frag, bias, 0.f, y, y_split, B, T_in, T_out, C_in, C_out, groups, s, range_flag, x_split);
-        return launch_mfma_spec<14, 18, 2, false, 2, 64>(x, w_frag, bias, 0.f, y, y_split, B, T_in, T_out, C_in, C_out, groups, s, range_flag, x_split);
-    }
-    if (C_in / groups == 10) return launch_mfma_spec<10, 14, 2, false, 4, 128>(x, w_frag, bias, 0.f, y, y_split, B, T_in, T_out, C_in, C_out, groups, s, range_flag, x_split);
-    return launch_mfma_spec<14, 18, 2, false, 2, 128>(x, w_frag, bias, 0.f, y, y_split, B, T_in, T_out, C_in, C_out, groups, s, range_flag, x_split);
+    GconvCall c = gconv_call(GE_S2_F16X3, B, T_in, C_in, C_out, groups, KS, x);
+    c.x_split = x_split; c.has_y = y != nullptr; c.has_y_split = y_split != nullptr;
+    GconvArgs a = {x, w_frag, bias, 0.f, y, y_split, range_flag, nullptr, T_in, C_in, C_out, groups, {}};
+    return launch_planned(c, a, s);
 }
 
 // reference Conv1d weight [C_out, CIG, K] -> packed [G][CIG][K][COG]

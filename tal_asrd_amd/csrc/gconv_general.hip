@@ -200,100 +200,61 @@ __global__ __launch_bounds__(256) void gconv_k_any_kernel(const float* __restric
 
 namespace {
 
-// dynamic LDS beyond the default 64 KB needs the attribute; set once per kernel for the largest k
-int reserve_lds(const void* kern, size_t bytes, bool& done) {
-    if (done) return TAL_OK;
-    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-        set_error("gconv_general: cannot reserve %zu bytes of LDS", bytes);
-        return TAL_EHIP;
+// one planned launch (csrc/gconv_plan.h) on this file's kernels; (CIG, COG, STRIDE, GB, TT, RESID) of gconv_k_kernel written once
+#define GCONV_K_SPECS(X) X(10, 14, 2, 4, 128, false) X(14, 18, 2, 2, 128, false) X(10, 10, 1, 2, 256, true) X(14, 14, 1, 2, 256, true) X(18, 18, 1, 2, 256, true)
+
+int launch_planned_k(const GconvCall& c, const float* x, const float* wp, const float* bias, float alpha, float* y, hipStream_t s) {
+    const GconvLaunch p = gconv_plan(c);
+    if (p.refusal) return gconv_refused(c, p.refusal);
+    if (p.grid_x == 0) return TAL_OK;
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+    switch (p.kernel) {
+        case GCK_K_TILED:
+#define X(CIG, COG, STRIDE, GB, TT, RESID)                                                                                                     \
+    if (p.cig == CIG && p.cog == COG && p.stride == STRIDE && p.gb == GB && p.tt == TT && p.resid == RESID)                                    \
+        return gconv_launch_planned<gconv_k_kernel<CIG, COG, STRIDE, GB, TT, RESID>>(p, grid, "gconv_general", s, x, wp, bias, alpha, y, c.T_in, \
+                                                                                     p.T_out, c.C_in, c.C_out, c.ks);
+            GCONV_K_SPECS(X)
+#undef X
+            break;
+        case GCK_K_C1:
+            if (p.tt == 32)
+                return gconv_launch_planned<gconv_k_c1_kernel<10, 20, 32>>(p, grid, "gconv_general (1 channel per group)", s, x, wp, bias, y, c.T_in, p.T_out,
+                                                                           c.C_in, c.C_out, c.ks);
+            return gconv_launch_planned<gconv_k_c1_kernel<10, 20, 128>>(p, grid, "gconv_general (1 channel per group)", s, x, wp, bias, y, c.T_in, p.T_out,
+                                                                        c.C_in, c.C_out, c.ks);
+        case GCK_K_ANY: {
+            const int64_t total = (int64_t)c.B * p.T_out * c.C_out;
+            if (p.resid)
+                return gconv_launch_planned<gconv_k_any_kernel<true>>(p, grid, "gconv_general (any width)", s, x, wp, bias, alpha, y, c.T_in, p.T_out, c.C_in,
+                                                                      c.C_out, p.cig, p.cog, p.stride, c.ks, total);
+            return gconv_launch_planned<gconv_k_any_kernel<false>>(p, grid, "gconv_general (any width)", s, x, wp, bias, alpha, y, c.T_in, p.T_out, c.C_in,
+                                                                   c.C_out, p.cig, p.cog, p.stride, c.ks, total);
+        }
+        default: break;
     }
-    done = true;
-    return TAL_OK;
+    set_error("gconv_general: the plan names a kernel that is not built (family %d, %d -> %d channels per group, stride %d, %d groups x %d steps)",
+              p.kernel, p.cig, p.cog, p.stride, p.gb, p.tt);
+    return TAL_EINVAL;
 }
-
-template <int CIG, int COG, int STRIDE, int GB, int TT, bool RESID>
-int launch_k_spec(const float* x, const float* wp, const float* bias, float alpha, float* y, int B, int64_t T_in, int64_t T_out,
-                  int C_in, int C_out, int groups, int ks, hipStream_t s) {
-    auto lds = [](int k) { return (size_t)GB * CIG * (size_t)(((TT - 1) * STRIDE + k) | 1) * sizeof(float); };
-    auto kern = gconv_k_kernel<CIG, COG, STRIDE, GB, TT, RESID>;
-    static bool attr = false;
-    int rc = reserve_lds(reinterpret_cast<const void*>(kern), lds(TAL_GCONV_MAX_K), attr);
-    if (rc) return rc;
-    dim3 grid((unsigned)cdiv(T_out, TT), (unsigned)(groups / GB), (unsigned)B);
-    ProfScope prof(RESID ? PROF_GCONV_RES : PROF_GCONV_S2, 2.0 * (double)B * (double)T_out * C_out * CIG * ks, s);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds(ks), s, x, wp, bias, alpha, y, T_in, T_out, C_in, C_out, ks);
-    TAL_CHECK_LAUNCH("gconv_general");
-    return TAL_OK;
-}
-
-template <int TT>
-int launch_k_c1(const float* x, const float* wp, const float* bias, float* y, int B, int64_t T_in, int64_t T_out, int C_in, int C_out,
-                int groups, int ks, hipStream_t s) {
-    constexpr int COG = 10, NG = 20;
-    auto lds = [](int k) { return ((size_t)((TT - 1) * 2 + k) * NG + (size_t)k * NG * COG) * sizeof(float); };
-    auto kern = gconv_k_c1_kernel<COG, NG, TT>;
-    static bool attr = false;
-    int rc = reserve_lds(reinterpret_cast<const void*>(kern), lds(TAL_GCONV_MAX_K), attr);
-    if (rc) return rc;
-    dim3 grid((unsigned)cdiv(T_out, TT), (unsigned)(groups / NG), (unsigned)B);
-    ProfScope prof(PROF_GCONV_S2, 2.0 * (double)B * (double)T_out * C_out * ks, s);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds(ks), s, x, wp, bias, y, T_in, T_out, C_in, C_out, ks);
-    TAL_CHECK_LAUNCH("gconv_general (1 channel per group)");
-    return TAL_OK;
-}
-
-template <bool RESID>
-int launch_k_any(const float* x, const float* wp, const float* bias, float alpha, float* y, int B, int64_t T_in, int64_t T_out,
-                 int C_in, int C_out, int groups, int stride, int ks, hipStream_t s) {
-    const int64_t total = (int64_t)B * T_out * C_out;
-    if (total == 0) return TAL_OK;
-    ProfScope prof(RESID ? PROF_GCONV_RES : PROF_GCONV_S2, 2.0 * (double)total * (C_in / groups) * ks, s);
-    hipLaunchKernelGGL(gconv_k_any_kernel<RESID>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, x, wp, bias, alpha, y, T_in,
-                       T_out, C_in, C_out, C_in / groups, C_out / groups, stride, ks, total);
-    TAL_CHECK_LAUNCH("gconv_general (any width)");
-    return TAL_OK;
-}
-
-bool aligned16(const float* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
 int launch_gconv_s2_k(const float* x, const float* wp, const float* bias, int B, int64_t T_in, int C_in, int C_out, int groups,
                       int ks, float* y, hipStream_t s) {
     TAL_CHECK_ARG(x && wp && bias && y, "tal_gconv_s2_k_fwd: null pointer");
-    TAL_CHECK_ARG(ks >= 1 && ks <= TAL_GCONV_MAX_K, "tal_gconv_s2_k_fwd: ksize=%d outside 1..%d", ks, TAL_GCONV_MAX_K);
-    TAL_CHECK_ARG(groups > 0 && C_in % groups == 0 && C_out % groups == 0, "tal_gconv_s2_k_fwd: channels %d->%d not divisible by groups %d",
-                  C_in, C_out, groups);
-    TAL_CHECK_ARG(B > 0 && T_in >= ks, "tal_gconv_s2_k_fwd: T_in=%lld shorter than the kernel (k=%d)", (long long)T_in, ks);
-    const int64_t T_out = (T_in - ks) / 2 + 1;
-    const int cig = C_in / groups, cog = C_out / groups;
-    const bool vec = C_in % 4 == 0 && aligned16(x);
-    if (cig == 1 && cog == 10 && groups % 20 == 0 && vec) {
-        // short inputs take 32-step tiles so that the launch covers the chip (as gconv_s2_c1_kernel)
-        if (cdiv(T_out, 128) * (groups / 20) * B < 256) return launch_k_c1<32>(x, wp, bias, y, B, T_in, T_out, C_in, C_out, groups, ks, s);
-        return launch_k_c1<128>(x, wp, bias, y, B, T_in, T_out, C_in, C_out, groups, ks, s);
-    }
-    if (cig == 10 && cog == 14 && groups % 4 == 0 && vec)
-        return launch_k_spec<10, 14, 2, 4, 128, false>(x, wp, bias, 0.f, y, B, T_in, T_out, C_in, C_out, groups, ks, s);
-    if (cig == 14 && cog == 18 && groups % 2 == 0 && vec)
-        return launch_k_spec<14, 18, 2, 2, 128, false>(x, wp, bias, 0.f, y, B, T_in, T_out, C_in, C_out, groups, ks, s);
-    return launch_k_any<false>(x, wp, bias, 0.f, y, B, T_in, T_out, C_in, C_out, groups, 2, ks, s);
+    GconvCall c = gconv_call(GE_S2_K, B, T_in, C_in, C_out, groups, ks, x);
+    c.has_y = true;
+    return launch_planned_k(c, x, wp, bias, 0.f, y, s);
 }
 
 int launch_gconv_res_k(const float* x, const float* wp, const float* bias, float alpha, int B, int64_t T, int C, int groups, int ks,
                        float* y, hipStream_t s) {
     TAL_CHECK_ARG(x && wp && bias && y, "tal_gconv_res_k_fwd: null pointer");
     TAL_CHECK_ARG(x != y, "tal_gconv_res_k_fwd: in-place not supported (halo reads)");
-    TAL_CHECK_ARG(ks >= 1 && ks <= TAL_GCONV_MAX_K && ks % 2 == 1, "tal_gconv_res_k_fwd: ksize=%d must be odd and in 1..%d", ks,
-                  TAL_GCONV_MAX_K);
-    TAL_CHECK_ARG(groups > 0 && C % groups == 0, "tal_gconv_res_k_fwd: C=%d not divisible by groups %d", C, groups);
-    TAL_CHECK_ARG(B > 0 && T > 0, "tal_gconv_res_k_fwd: bad shape");
-    const int cg = C / groups;
-    const bool vec = C % 4 == 0 && aligned16(x) && groups % 2 == 0;
-    if (cg == 10 && vec) return launch_k_spec<10, 10, 1, 2, 256, true>(x, wp, bias, alpha, y, B, T, T, C, C, groups, ks, s);
-    if (cg == 14 && vec) return launch_k_spec<14, 14, 1, 2, 256, true>(x, wp, bias, alpha, y, B, T, T, C, C, groups, ks, s);
-    if (cg == 18 && vec) return launch_k_spec<18, 18, 1, 2, 256, true>(x, wp, bias, alpha, y, B, T, T, C, C, groups, ks, s);
-    return launch_k_any<true>(x, wp, bias, alpha, y, B, T, T, C, C, groups, 1, ks, s);
+    GconvCall c = gconv_call(GE_RES_K, B, T, C, C, groups, ks, x);
+    c.has_y = true;
+    return launch_planned_k(c, x, wp, bias, alpha, y, s);
 }
 
 }  // namespace tal
