@@ -866,6 +866,70 @@ int tal_edit_align_fwd(const int64_t* desc_host, const int64_t* desc_dev, int P,
                        int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Speaker turns (csrc/turns.hip): per-frame speaker ids -> smoothed who-spoke-when turns, and the mean feature
+ * of each.  ids int32 [N] hold the frames of B items back to back; item b owns [offsets[b], offsets[b + 1])
+ * (offsets int64 [B + 1], ascending from 0, an item may be empty; N = offsets[B]).  Integer arithmetic on
+ * every decision: each integer output is exact.
+ *   a. MODE FILTER, half window w = smooth in [0, TAL_TURNS_MAX_HALF]: the window of frame t is [t - w, t + w]
+ *      clipped to its item (it never reads another item's frames); s[t] = the id with the most occurrences in
+ *      it.  TIE RULE: among the ids tied for the most, ids[t] itself if it is one of them, else the smallest
+ *      id.  w = 0 gives s = ids.
+ *   b. RUNS: maximal runs of equal s inside an item.
+ *   c. MINIMUM DURATION, one pass, m = min_frames >= 1: a run of fewer than m frames is short, the others are
+ *      long.  A short run takes the label of the nearest long run BEFORE it in the same item; if there is
+ *      none, of the nearest long run AFTER it in the same item; an item without a long run keeps its runs.
+ *      Adjacent runs of equal label are then merged into turns.  (In an item that has a long run every turn is
+ *      at least m frames long.)
+ *   d. Per turn k: start[k] / end[k] in frames relative to the item (end exclusive), label[k], and purity[k] =
+ *      the number of frames of the turn whose RAW ids[t] equals the label.  Turns are stored item after item:
+ *      item b owns turns [turn_offsets[b], turn_offsets[b + 1]), turn_offsets int64 [B + 1].
+ *   e. frame_labels int32 [N] (may be NULL): the label of the turn that holds each frame.
+ *   f. turn_ranges int64 [N, 2] (may be NULL): per turn its first frame and the one behind its last as indices
+ *      into ids -- the `ranges` of tal_segment_mean_fwd for the turn embeddings, with max_rows = N.
+ * BOUNDS: the number of turns depends on the data and is at most N: start, end, label and purity are caller
+ * buffers of N int32 each, of which the first turn_offsets[B] entries are written.  N <= 2^31 - 1 - 2 tiles - 2
+ * halos; indices are int32.  offsets travels twice: the host copy is checked before anything is launched, the
+ * device copy is what the kernels read.
+ * STATUS: *status (device int32) is cleared by the call; bit 0 is raised when an id lies outside [0, num_ids).
+ * The kernels behind the mode filter then return at once and NO output of the call is defined (turn_offsets
+ * included): read the status word before anything else.  No kernel indexes memory by an id.
+ * The call is a fixed sequence of 11 launches on `stream` (count -> scan -> scatter three times over; tiles of
+ * the length tal_speaker_turns_tile reports, one workgroup per tile); no kernel waits for another workgroup.
+ * The workspace (tal_speaker_turns_workspace_bytes(N), 16-byte aligned) needs no initialising and keeps nothing
+ * between calls.  A short workspace is TAL_ENOMEM, smooth / min_frames / num_ids / offsets out of range
+ * TAL_EINVAL; both launch nothing.  N == 0 writes turn_offsets = 0 and is TAL_OK.
+ *
+ * tal_segment_mean_fwd: out[g] = the mean of the rows [ranges[2g], ranges[2g + 1]) of feat [N, E] (fp32, row
+ * pitch E), for G ranges (device int64 [G, 2], any order, overlaps allowed; an empty range gives zeros).  Not
+ * normalised.  E a multiple of 4 in [4, 1024]; feat and out 16-byte aligned.
+ *   ORDER OF ADDITION, fixed by (range, E) alone: a range is cut into chunks of TAL_SEGMENT_MEAN_CHUNK rows
+ *   counted from its own start; a chunk is summed by E / 4 column threads x S = 256 / (E / 4) row slots, slot j
+ *   adding rows j, j + S, ... in order, then the slots' sums are added in slot order; the chunk sums are added
+ *   in chunk order and divided by the row count.  No floating-point atomics: the result is bit-identical call
+ *   after call, for any launch grid and whatever other ranges share the call.  A long range is spread over as
+ *   many workgroups as it has chunks.
+ *   max_rows: the caller's bound on the summed length of the ranges (N for ranges that do not overlap); it sizes
+ *   the chunk sums in the workspace (tal_segment_mean_workspace_bytes(G, max_rows, E)).
+ *   *status (device int32, cleared by the call): bit 0 = a range is not 0 <= start <= end <= N, bit 1 = the
+ *   ranges have more chunks than G + max_rows / TAL_SEGMENT_MEAN_CHUNK.  With either bit `out` is undefined
+ *   and nothing outside the buffers was touched.  G == 0 is TAL_OK.
+ * ------------------------------------------------------------------ */
+#define TAL_TURNS_MAX_HALF 31
+#define TAL_SEGMENT_MEAN_CHUNK 128
+#define TAL_TURNS_STATUS_BAD_ID 1
+#define TAL_SEGMENT_MEAN_STATUS_BAD_RANGE 1
+#define TAL_SEGMENT_MEAN_STATUS_TOO_MANY_CHUNKS 2
+void tal_speaker_turns_tile(int* tile, int* max_half);
+size_t tal_speaker_turns_workspace_bytes(int64_t N);
+int tal_speaker_turns_fwd(const int32_t* ids, const int64_t* offsets_host, const int64_t* offsets_dev, int B, int num_ids,
+                          int smooth, int min_frames, int32_t* start, int32_t* end, int32_t* label, int32_t* purity,
+                          int32_t* frame_labels, int64_t* turn_ranges, int64_t* turn_offsets, int32_t* status,
+                          void* workspace, size_t workspace_bytes, void* stream);
+size_t tal_segment_mean_workspace_bytes(int64_t G, int64_t max_rows, int E);
+int tal_segment_mean_fwd(const float* feat, int64_t N, int E, const int64_t* ranges, int64_t G, int64_t max_rows,
+                         float* out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Measurement hooks (bench.py): when enabled, every launch of the hot kernels
  * is bracketed by two hipEvents on its launch stream.  class: 0 dense-layer
  * GEMM, 1 TDSBlock grouped conv, 2 stride-2 grouped conv, 3 log-mel, 4 other.

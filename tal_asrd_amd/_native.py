@@ -185,6 +185,11 @@ SIGNATURES = {
     "tal_edit_align_workspace_bytes": (_sz, [_i, _p, _p, _i]),
     "tal_edit_align_plan": (_i, [_i, _p, _p, _i, _p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "tal_edit_align_fwd": (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "tal_speaker_turns_tile": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tal_speaker_turns_workspace_bytes": (_sz, [_i64]),
+    "tal_speaker_turns_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "tal_segment_mean_workspace_bytes": (_sz, [_i64, _i64, _i]),
+    "tal_segment_mean_fwd": (_i, [_p, _i64, _i, _p, _i64, _i64, _p, _p, _p, _sz, _p]),
     "tal_prof_enable": (_i, [_i]),
     "tal_prof_reset": (_i, []),
     "tal_prof_collect": (_i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

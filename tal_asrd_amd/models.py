@@ -608,6 +608,29 @@ class SDModel(_Resampled, nn.Module):
             return (feat,) + ops.soft_embed(feat, self.spk_logit_proj.weight, self.spk_logit_proj.bias, None, want_lse=True)
         return self.encoder.forward_then(mel, head, x_mean=mean, split_ok=self._embed_split() is not None)
 
+    @torch.no_grad()
+    def speaker_turns(self, x_wav, smooth=6, min_frames=13, want_embeds=True, sample_rate=None):
+        """Who spoke when: speaker_ids, then ops.speaker_turns on its ids (and features) on the same stream, nothing copied to the
+        host in between -> ops.SpeakerTurns (offsets, start, end, label, purity, embed, frame_labels; rttm.turns_to_seconds /
+        rttm.write_rttm turn it into text).  Every row of a batched call is one item.  Per frame the most frequent id within
+        +-smooth frames, runs shorter than min_frames absorbed by the nearest long run (before first), one mean feature per turn
+        (want_embeds; not normalised).  The defaults are about 1 s of smoothing (13 frames) and a 1 s minimum turn at 0.08 s per
+        frame: STARTING VALUES, nothing has been tuned to them.  Input forms as speaker_ids."""
+        rs = self._resampler(sample_rate)
+        if rs is not None:
+            x_wav = rs(x_wav)
+        mel, mean = self.logmelspec.forward_unsubtracted(x_wav)
+        return self.speaker_turns_from_logmel(mel, mean, smooth=smooth, min_frames=min_frames, want_embeds=want_embeds)
+
+    @torch.no_grad()
+    def speaker_turns_from_logmel(self, mel, mean, smooth=6, min_frames=13, want_embeds=True):
+        """The same from the log-mel before its mean subtraction and the scalar to subtract (see speaker_ids_from_logmel)."""
+        feat, ids = self.speaker_ids_from_logmel(mel, mean)
+        frames = ids.shape[-1] if ids.dim() else 1
+        items = ids.numel() // frames if frames else 0
+        return ops.speaker_turns(ids, self.spk_logit_proj.weight.shape[0], offsets=[b * frames for b in range(items + 1)],
+                                 smooth=smooth, min_frames=min_frames, feat=feat if want_embeds else None, want_frames=True)
+
     def _embed_split(self):
         """hi / lo fp16 split of spk_embed_proj.weight (None: a weight outside the fp16 range, or a width the fp16x3 layer does not
         take -- the head then runs its fp32 embedding layer on the fp32 encoder output)."""

@@ -853,3 +853,140 @@ def edit_align(a, b, a_labels=None, b_labels=None, n_labels=None, want_path=True
             launches += nl.value
             ws_max = max(ws_max, nws.value)
     return EditAlignment(stats, path, path_off, counts, launches, ws_max)
+
+
+# ------------------------------------------------------------------ speaker turns
+TURNS_MAX_HALF = 31              # TAL_TURNS_MAX_HALF: largest half window of the mode filter
+SEGMENT_MEAN_CHUNK = 128         # TAL_SEGMENT_MEAN_CHUNK: rows of a chunk of segment_mean's fixed summation order
+TURNS_MAX_FRAMES = 2 ** 31 - 1 - 2 * 256 - 2 * TURNS_MAX_HALF
+
+
+def speaker_turns_tile():
+    """(tile, max_half): frames per workgroup of the speaker-turn kernels and the largest half window (tal_speaker_turns_tile)."""
+    t, h = C.c_int(), C.c_int()
+    N.lib().tal_speaker_turns_tile(C.byref(t), C.byref(h))
+    return t.value, h.value
+
+
+class SpeakerTurns:
+    """Result of speaker_turns for B items, everything on the device.  Item b owns the turns [offsets[b], offsets[b + 1]) (int64
+    [B + 1]); per turn: start / end (int32, frames relative to the item, end exclusive), label (int32), purity (int32: frames of
+    the turn whose raw id equals the label), embed (fp32 [turns, E], the mean of the turn's feature rows, NOT normalised -- or None
+    without feat); frame_labels (int32 [N], the label of the turn that holds each frame -- or None without want_frames)."""
+
+    def __init__(self, offsets, start, end, label, purity, embed, frame_labels):
+        self.offsets, self.start, self.end, self.label, self.purity = offsets, start, end, label, purity
+        self.embed, self.frame_labels = embed, frame_labels
+
+    @property
+    def num_turns(self):
+        return int(self.start.numel())
+
+
+def _segment_mean(feat, ranges, max_rows, check):
+    lib = N.lib()
+    Nf, E = feat.shape
+    G = ranges.shape[0]
+    out = torch.empty(G, E, dtype=torch.float32, device=feat.device)
+    if G == 0:
+        return out
+    nws = lib.tal_segment_mean_workspace_bytes(G, max_rows, E)
+    if nws == 0:
+        raise N.NativeError("segment_mean: %d ranges over %d rows of width %d: the width must be a multiple of 4 in [4, 1024]" % (G, max_rows, E))
+    ws = _ws(nws, feat.device)
+    status = torch.empty(1, dtype=torch.int32, device=feat.device)
+    N.check(lib.tal_segment_mean_fwd(N.ptr(feat), Nf, E, N.ptr(ranges), G, max_rows, N.ptr(out), N.ptr(status), N.ptr(ws), nws,
+                                     N.stream_handle()), "tal_segment_mean_fwd")
+    if check:
+        st = int(status.item())
+        if st & 1:
+            raise N.NativeError("segment_mean: a range is not 0 <= start <= end <= %d" % Nf)
+        if st & 2:
+            raise N.NativeError("segment_mean: the ranges cover more than the %d rows their workspace was sized for" % max_rows)
+    return out
+
+
+def segment_mean(feat, ranges):
+    """feat [N, E] fp32, ranges [G, 2] (integers, host or device; any order, overlaps allowed) -> [G, E]: out[g] = the mean of
+    feat[ranges[g, 0] : ranges[g, 1]], zeros for an empty range (tal_segment_mean_fwd).  The order of every addition is fixed by the
+    range and E alone (chunks of SEGMENT_MEAN_CHUNK rows counted from the range's start, added in chunk order), so the result is
+    bit-identical call after call and whatever other ranges share the call.  E: a multiple of 4 up to 1024.  A range outside
+    [0, N] raises.  One small device-to-host read per call (the summed range length, when the ranges live on the device, and the
+    status word)."""
+    feat = _f32c(feat, "segment_mean")
+    if feat.dim() != 2:
+        raise N.NativeError("segment_mean: feat must be [N, E], got %s" % (tuple(feat.shape),))
+    if not torch.is_tensor(ranges):
+        ranges = torch.as_tensor(ranges)
+    if ranges.dtype.is_floating_point or ranges.dtype == torch.bool or ranges.numel() % 2 or (ranges.numel() and (ranges.dim() != 2 or ranges.shape[1] != 2)):
+        raise N.NativeError("segment_mean: ranges must be integers of shape [G, 2], got %s %s" % (ranges.dtype, tuple(ranges.shape)))
+    ranges = ranges.reshape(-1, 2).to(torch.int64)
+    rows = int((ranges[:, 1] - ranges[:, 0]).clamp_(min=0).sum()) if ranges.numel() else 0
+    return _segment_mean(feat, ranges.to(feat.device).contiguous(), rows, True)
+
+
+def speaker_turns(ids, num_ids, offsets=None, smooth=0, min_frames=1, feat=None, want_frames=False):
+    """Per-frame speaker ids -> who-spoke-when turns on the device (tal_speaker_turns_fwd) -> SpeakerTurns.
+
+    ids: int32 device tensor, the frames of B items back to back (any shape: it is flattened); offsets: B + 1 ascending host integers
+    from 0 to ids.numel() (list / array / CPU tensor; a device tensor is copied to the host), item b = ids[offsets[b] : offsets[b + 1]],
+    an item may be empty; None = one item.  Every id must lie in [0, num_ids): one outside raises NativeError and nothing is returned.
+      1. mode filter, half window `smooth` in [0, 31]: each frame takes the most frequent id of [t - smooth, t + smooth] clipped to
+         its item; among ids tied for the most, the frame's own id if it is one of them, else the smallest.
+      2. maximal runs of equal filtered ids inside an item; a run shorter than `min_frames` takes the label of the nearest run of at
+         least min_frames frames before it in the item, else of the nearest such run after it; an item without such a run keeps its
+         runs; adjacent runs of equal label merge into turns.
+      3. per turn start / end / label / purity, and with feat [N, E] (fp32, E a multiple of 4 up to 1024) embed = the mean of the
+         turn's rows (segment_mean's fixed order; not normalised -- torch.nn.functional.normalize is the caller's line).
+    Integer outputs are exact.  One device-to-host read per call (the number of turns with the status word, 16 bytes); the
+    per-turn tensors are views of that length into buffers sized for the bound (one turn per frame)."""
+    lib = N.lib()
+    N.require_cuda(ids, "speaker_turns")
+    if ids.dtype != torch.int32:
+        raise N.NativeError("speaker_turns: ids must be int32 (SDModel.speaker_ids' ids), got %s" % ids.dtype)
+    for name, v, lo in (("num_ids", num_ids, 1), ("smooth", smooth, 0), ("min_frames", min_frames, 1)):
+        if isinstance(v, bool) or int(v) != v or int(v) < lo or int(v) > 2 ** 31 - 1:
+            raise N.NativeError("speaker_turns: %s=%r must be an integer >= %d" % (name, v, lo))
+    if int(smooth) > TURNS_MAX_HALF:
+        raise N.NativeError("speaker_turns: smooth=%d outside [0, %d]" % (smooth, TURNS_MAX_HALF))
+    dev = ids.device
+    ids = ids.contiguous().reshape(-1)
+    n = ids.numel()
+    import numpy as np
+    if offsets is None:
+        off = np.array([0, n], np.int64)
+    else:
+        off = np.ascontiguousarray((offsets.detach().cpu() if torch.is_tensor(offsets) else torch.as_tensor(np.asarray(offsets))).numpy()
+                                   .astype(np.int64).reshape(-1))
+    B = len(off) - 1
+    if B < 0 or off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
+        raise N.NativeError("speaker_turns: offsets must ascend from 0 to ids.numel() = %d" % n)
+    if n > TURNS_MAX_FRAMES or B > 2 ** 31 - 2:
+        raise N.NativeError("speaker_turns: %d frames in %d items (at most %d frames per call)" % (n, B, TURNS_MAX_FRAMES))
+    if feat is not None:
+        feat = _f32c(feat, "speaker_turns(feat)")
+        if feat.dim() < 2 or feat.numel() != n * feat.shape[-1] or feat.device != dev:
+            raise N.NativeError("speaker_turns: feat %s does not hold one row per frame (%d frames on %s)" % (tuple(feat.shape), n, dev))
+        feat = feat.reshape(n, feat.shape[-1])
+        if feat.shape[1] % 4 or not 4 <= feat.shape[1] <= 1024:
+            raise N.NativeError("speaker_turns: feat rows of %d floats (a multiple of 4 in [4, 1024])" % feat.shape[1])
+    off_dev = torch.from_numpy(off).to(dev)
+    buf = torch.empty(4, max(n, 1), dtype=torch.int32, device=dev)
+    frames = torch.empty(n, dtype=torch.int32, device=dev) if want_frames else None
+    ranges = torch.empty(n, 2, dtype=torch.int64, device=dev) if feat is not None else None      # the turns' rows of feat
+    meta = torch.zeros(B + 2, dtype=torch.int64, device=dev)      # turn_offsets [B + 1], then the status word
+    status = meta[B + 1:].view(torch.int32)
+    nws = lib.tal_speaker_turns_workspace_bytes(n)
+    ws = _ws(nws, dev)
+    N.check(lib.tal_speaker_turns_fwd(N.ptr(ids), off.ctypes.data, N.ptr(off_dev), B, int(num_ids), int(smooth), int(min_frames),
+                                      N.ptr(buf[0]), N.ptr(buf[1]), N.ptr(buf[2]), N.ptr(buf[3]), N.ptr(frames), N.ptr(ranges), N.ptr(meta), N.ptr(status),
+                                      N.ptr(ws), nws, N.stream_handle()), "tal_speaker_turns_fwd")
+    total, st = meta[B:].tolist()      # the one read-back
+    if st & 1:
+        raise N.NativeError("speaker_turns: an id lies outside [0, %d)" % num_ids)
+    start, end, label, purity = (buf[i, :total] for i in range(4))
+    embed = None
+    if feat is not None:
+        # (the ranges are the call's own turns: inside [0, n] and n rows together, so the status word needs no second read)
+        embed = _segment_mean(feat, ranges[:total], n, False)
+    return SpeakerTurns(meta[:B + 1], start, end, label, purity, embed, frames)
