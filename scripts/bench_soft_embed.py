@@ -13,8 +13,8 @@ speaker columns: w = values = embedding.weight[10000:], no bias, on already proj
   baseline   (128) ops.sd_head(want_logits=True) + torch.softmax + torch.matmul, with "features only (sd_head)" listed beside it:
              the baseline includes the 1440 -> 128 embedding layer, the two forms start from its output;
              (64) ops.linear onto all 16008 columns + torch.softmax of the speaker columns + torch.matmul
---sweep times both forms over a ladder of row counts at both widths: the auto threshold of the dispatch (FUSED_FROM_ROWS_* in
-csrc/soft_embed.hip) is the smallest row count of the ladder from which the fused form is the faster one at every larger count.
+--sweep times both forms over a ladder of row counts at both widths: the auto threshold of the dispatch (SOFT_FUSED_FROM_ROWS_* in
+csrc/head_plan.h) is the smallest row count of the ladder from which the fused form is the faster one at every larger count.
 The last section runs the case table of tests/_soft_embed_ref.py through both forms and prints the largest error-to-bound ratio."""
 import argparse
 import os

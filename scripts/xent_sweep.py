@@ -11,7 +11,7 @@ Every (shape, path) pair runs in a process of its own under its own time limit; 
 sweep (nothing more is started on the device after it).  A child times each row count as the median of `passes` device-event windows of
 `iters` back-to-back calls behind 2 untimed ones, and reports the peak extra device memory of one call (torch's allocator: the
 workspaces and today's logits all come from it) and, for the two new paths, the largest difference from today's path's result.
-The auto threshold of the dispatch (FUSED_FROM_ROWS in csrc/xent.hip) is read off the table this prints."""
+The auto threshold of the dispatch (XENT_FUSED_FROM_ROWS_* in csrc/head_plan.h) is read off the table this prints."""
 import argparse
 import json
 import os

@@ -9,6 +9,7 @@
 #include "../../include/tal_asrd.h"
 #include "gemm_plan.h"
 #include "gconv_plan.h"
+#include "head_plan.h"
 
 namespace tal {
 
@@ -230,30 +231,46 @@ inline int launch_linear_ld(const float* a, int64_t lda, const float* w, const f
     return launch_gemm(g, 0, 1, s);
 }
 
-// ---- the D -> E0 projection in front of an LM head that runs on the projected rows (tal_lm_xent_fwd, tal_lm_soft_embed_fwd) ----
-// the projected rows [M, E0] take the head of the workspace, rounded up to 16 bytes
-inline size_t lm_proj_bytes(int64_t M, int E0) { return ((size_t)M * E0 * sizeof(float) + 15) & ~(size_t)15; }
-// t = h . proj_t^T into the head of the workspace, then stage(t, the rest of the workspace, its bytes).  check(t, need) holds the
-// second stage's own refusals and gives the bytes it needs: it runs before the projection is launched -- a refused call launches nothing.
-template <class Check, class Stage>
-int lm_head_project(const char* who, const float* h, int64_t M, int64_t ldh, int D, const float* proj_t, int E0, void* workspace,
-                    size_t workspace_bytes, hipStream_t s, Check check, Stage stage) {
-    const size_t head = lm_proj_bytes(M, E0);
-    if (!workspace || workspace_bytes < head) {
-        set_error("%s: workspace %zu < %zu bytes", who, workspace ? workspace_bytes : (size_t)0, head);
+// ---- the streaming heads: every call is decided by head_call_plan (head_plan.h) ----
+// the facts of a call: the head's two options and the CU count are read here and nowhere below (a query: no operands, no workspace)
+inline HeadCall head_call(int entry, int64_t M, int N, int E, int D, int k, int64_t ldf, int proj_in = 0, const void* feat = nullptr,
+                          const void* w = nullptr, const void* values = nullptr, const void* workspace = nullptr, size_t workspace_bytes = 0) {
+    const auto lo = [](const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15); };
+    const bool topk = entry == HE_TOPK, xent = entry == HE_XENT_ROWS || entry == HE_LM_XENT;
+    return {entry, M, N, E, D, k, ldf, proj_in, values != w, lo(feat), lo(w), lo(values), lo(workspace), workspace ? workspace_bytes : 0,
+            opt(topk ? OPT_HEAD_TOPK_FORM : xent ? OPT_XENT_FORM : OPT_SOFT_EMBED_FORM),
+            opt(topk ? OPT_HEAD_TOPK_GRID : xent ? OPT_XENT_GRID : OPT_SOFT_EMBED_GRID), device_cus()};
+}
+// a refused plan's message; returns TAL_ENOMEM for a short workspace, else TAL_EINVAL
+inline int head_refused(const HeadCall& c, const HeadLaunch& p) {
+    char text[256];
+    head_refusal_text(c, p, text, sizeof text);
+    set_error("%s", text);
+    return p.refusal == HR_WS_SHORT ? TAL_ENOMEM : TAL_EINVAL;
+}
+// A head on the rows of h [M, ldh] or -- proj_t != NULL: an LM head behind its D -> E0 projection -- on t = h . proj_t^T, which
+// takes the head of the workspace.  call(feat, ldf, E, proj_in, ws, ws_bytes) fills the HeadCall of the head on those rows and on the
+// workspace behind them; the plan is made, and a refused call refused, before the projection is launched -- a refused call launches
+// nothing -- and run(c, p, feat, ws) runs that plan.
+template <class Call, class Run>
+int head_on_rows(int entry, const float* h, int64_t M, int64_t ldh, int D, const float* proj_t, int E0, void* workspace, size_t workspace_bytes,
+                 hipStream_t s, Call call, Run run) {
+    const size_t head = proj_t ? lm_proj_bytes(M, E0) : 0;
+    if (head && (!workspace || workspace_bytes < head)) {
+        set_error("%s: workspace %zu < %zu bytes", head_entry_name(entry), workspace ? workspace_bytes : (size_t)0, head);
         return TAL_ENOMEM;
     }
     float* t = reinterpret_cast<float*>(workspace);
-    size_t need = 0;
-    int rc = check(t, need);
-    if (rc) return rc;
-    if (workspace_bytes < head + need) {
-        set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, head + need);
+    void* rest = reinterpret_cast<char*>(workspace) + head;
+    const HeadCall c = proj_t ? call(t, (int64_t)E0, E0, D, rest, workspace_bytes - head) : call(h, ldh, D, 0, rest, workspace_bytes);
+    const HeadLaunch p = head_call_plan(c);
+    if (p.refusal == HR_WS_SHORT && head) {       // (the message counts the projected rows in)
+        set_error("%s: workspace %zu < %zu bytes", head_entry_name(entry), workspace_bytes, head + p.need);
         return TAL_ENOMEM;
     }
-    rc = launch_linear_ld(h, ldh, proj_t, nullptr, M, E0, D, t, E0, s);
-    if (rc) return rc;
-    return stage(t, reinterpret_cast<char*>(workspace) + head, workspace_bytes - head);
+    if (p.refusal) return head_refused(c, p);
+    const int rc = proj_t ? launch_linear_ld(h, ldh, proj_t, nullptr, M, E0, D, t, E0, s) : TAL_OK;
+    return rc ? rc : run(c, p, proj_t ? t : h, rest);
 }
 
 // internal launchers shared between translation units

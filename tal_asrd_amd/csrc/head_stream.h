@@ -29,8 +29,7 @@
 
 namespace tal {
 
-constexpr int HS_BM = 128, HS_BN = 128, HS_NSUB = 4;
-constexpr int HS_SLOTS = 16;         // most workgroup slots per row
+constexpr int HS_NSUB = 4;           // 32-column sub-tiles of an N tile (HS_BM, HS_BN, HS_SLOTS: csrc/head_plan.h)
 constexpr int HS_PITCH = 33;         // row pitch (floats) of a wave's 32 x 32 logit tile
 constexpr int NOIDX = 0x7fffffff;
 

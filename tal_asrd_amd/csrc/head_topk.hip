@@ -17,13 +17,6 @@ namespace tal {
 
 namespace {
 
-constexpr int TK = 128;             // feature width (K) of the fused form
-
-// rows at and above which auto dispatch takes the fused form for E = 128: the smallest row count of the sweep in
-// profiles/head_topk.txt at which it measured faster than the generic form (2048 rows: generic 0.114 ms, fused 0.126;
-// 3751 rows: 0.225 / 0.176)
-constexpr int64_t FUSED_FROM_ROWS = 3751;
-
 // (TV / TI: K floats / ints under [], an array or a vector)
 template <int K, class TV, class TI>
 __device__ __forceinline__ void topk_clear(TV& tv, TI& ti) {
@@ -167,17 +160,6 @@ __global__ __launch_bounds__(256) void topk_lse_rows_kernel(const float* __restr
     wave_finish<K>(tv, ti, mx, sm, k, row, lane, ids, logp, lse);
 }
 
-int list_len(int k) {       // the kernels keep lists of 1, 2, 4, 8 or 16 entries
-    int K = 1;
-    while (K < k) K *= 2;
-    return K;
-}
-
-// two workgroups per CU by default
-RunPlan topk_plan(int64_t M, int S) { return head_plan(M, S, HS_BM, HS_BN, HS_SLOTS, 2, device_cus(), opt(OPT_HEAD_TOPK_GRID)); }
-
-size_t fused_ws_bytes(int64_t M, int S, int k) { return (size_t)M * topk_plan(M, S).hp * 2 * ((size_t)list_len(k) * 8 + 8); }
-
 #define TOPK_DISPATCH(K_, CALL)                       \
     switch (K_) {                                     \
         case 1: { constexpr int KK = 1; CALL; } break;   \
@@ -195,32 +177,23 @@ int launch_topk_lse_rows(const float* x, int64_t M, int N, int k, int32_t* ids, 
     return TAL_OK;
 }
 
-int launch_head_topk(const float* feat, const float* w, const float* b, int64_t M, int S, int k, int32_t* ids, float* logp, float* lse,
-                     void* workspace, hipStream_t s) {
-    const int NT = (int)cdiv(S, HS_BN), K = list_len(k);
-    const int64_t U = cdiv(M, HS_BM) * NT;
-    const RunPlan plan = topk_plan(M, S);
-    const int64_t grid = plan.grid;
-    const int hp = plan.hp;
-    float* pv = reinterpret_cast<float*>(workspace);
-    int32_t* pi = reinterpret_cast<int32_t*>(pv + (size_t)M * hp * 2 * K);
-    float* pms = reinterpret_cast<float*>(pi + (size_t)M * hp * 2 * K);
+// the fused launch the plan describes
+int launch_head_topk(const HeadLaunch& p, const float* feat, const float* w, const float* b, int64_t M, int S, int k, int32_t* ids,
+                     float* logp, float* lse, void* workspace, hipStream_t s) {
+    char* ws = reinterpret_cast<char*>(workspace);
+    const TopkParts parts = {reinterpret_cast<float*>(ws + p.off[0]), reinterpret_cast<int32_t*>(ws + p.off[1]), reinterpret_cast<float*>(ws + p.off[2])};
+    const int64_t grid = p.run.grid;
     {
         ProfScope prof(PROF_GEMM, 2.0 * (double)M * (double)S * TK, s);
-        const TopkParts parts = {pv, pi, pms};
-        TOPK_DISPATCH(K, hipLaunchKernelGGL((head_stream_kernel<TK, TopkScan<KK>>), dim3((unsigned)grid), dim3(256), 0, s, feat, (int64_t)TK, w, b,
-                                            M, S, NT, U, parts, hp));
+        TOPK_DISPATCH(p.K, hipLaunchKernelGGL((head_stream_kernel<TK, TopkScan<KK>>), dim3((unsigned)grid), dim3(256), 0, s, feat, (int64_t)TK, w, b,
+                                              M, S, p.NT, p.U, parts, p.run.hp));
         TAL_CHECK_LAUNCH("head_topk");
     }
-    ProfScope prof(PROF_OTHER, (double)M * hp * 2 * (K * 8.0 + 8.0), s);
-    TOPK_DISPATCH(K, hipLaunchKernelGGL(head_topk_merge_kernel<KK>, dim3((unsigned)cdiv(M, 4)), dim3(256), 0, s, pv, pi, pms, M, NT, U, grid, hp, k,
-                                        ids, logp, lse));
+    ProfScope prof(PROF_OTHER, (double)p.need, s);
+    TOPK_DISPATCH(p.K, hipLaunchKernelGGL(head_topk_merge_kernel<KK>, dim3((unsigned)cdiv(M, 4)), dim3(256), 0, s, parts.part_val, parts.part_idx, parts.part_ms, M, p.NT, p.U, grid,
+                                          p.run.hp, k, ids, logp, lse));
     TAL_CHECK_LAUNCH("head_topk(merge)");
     return TAL_OK;
-}
-
-bool fused_possible(const float* feat, const float* w, int E) {
-    return E == TK && ((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(w)) & 15) == 0;
 }
 
 }  // namespace
@@ -229,12 +202,7 @@ bool fused_possible(const float* feat, const float* w, int E) {
 
 using namespace tal;
 
-extern "C" size_t tal_spk_topk_workspace_bytes(int64_t M, int S, int E, int k) {
-    if (M <= 0 || S <= 0 || E <= 0 || k < 1 || k > TAL_TOPK_MAX) return 0;
-    const size_t generic = (size_t)generic_chunk_rows(M, S) * (size_t)S * 4;
-    const size_t fused = E == TK ? fused_ws_bytes(M, S, k) : 0;
-    return generic > fused ? generic : fused;
-}
+extern "C" size_t tal_spk_topk_workspace_bytes(int64_t M, int S, int E, int k) { return head_query_bytes(head_call(HE_TOPK, M, S, E, E, k, E)); }
 
 extern "C" int tal_spk_topk_fwd(const float* feat, int64_t M, int E, const float* w_logit, const float* b_logit, int S, int k,
                                 int32_t* ids, float* logp, float* lse, void* workspace, size_t workspace_bytes, void* stream) {
@@ -243,27 +211,16 @@ extern "C" int tal_spk_topk_fwd(const float* feat, int64_t M, int E, const float
     if (M == 0) return TAL_OK;
     TAL_CHECK_ARG(feat && w_logit && ids && logp, "tal_spk_topk_fwd: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    const int form = opt(OPT_HEAD_TOPK_FORM);
-    TAL_CHECK_ARG(form != 2 || fused_possible(feat, w_logit, E),
-                  "tal_spk_topk_fwd: the fused form needs E == %d and 16-byte aligned operands (E=%d)", TK, E);
-    const bool fused = form == 2 || (form == 0 && fused_possible(feat, w_logit, E) && M >= FUSED_FROM_ROWS);
-    const size_t need = fused ? fused_ws_bytes(M, S, k) : (size_t)generic_chunk_rows(M, S) * (size_t)S * 4;
-    if (!workspace || workspace_bytes < need) {
-        set_error("tal_spk_topk_fwd: workspace %zu < %zu bytes", workspace ? workspace_bytes : (size_t)0, need);
-        return TAL_ENOMEM;
-    }
-    if (fused) return launch_head_topk(feat, w_logit, b_logit, M, S, k, ids, logp, lse, workspace, s);
+    const HeadCall c = head_call(HE_TOPK, M, S, E, E, k, E, 0, feat, w_logit, w_logit, workspace, workspace_bytes);
+    const HeadLaunch p = head_call_plan(c);
+    if (p.refusal) return head_refused(c, p);
+    if (p.fused) return launch_head_topk(p, feat, w_logit, b_logit, M, S, k, ids, logp, lse, workspace, s);
     // the logits of a chunk of rows through the dense layer, then the row kernel
-    const int64_t chunk = generic_chunk_rows(M, S);
     float* logits = reinterpret_cast<float*>(workspace);
-    for (int64_t r0 = 0; r0 < M; r0 += chunk) {
-        const int64_t rows = M - r0 < chunk ? M - r0 : chunk;
-        int rc = launch_linear(feat + r0 * E, w_logit, b_logit, nullptr, 0.f, 0, rows, S, E, logits, s);
-        if (rc) return rc;
-        rc = launch_topk_lse_rows(logits, rows, S, k, ids + r0 * k, logp + r0 * k, lse ? lse + r0 : nullptr, s);
-        if (rc) return rc;
-    }
-    return TAL_OK;
+    return for_row_chunks(M, p.chunk, [&](int64_t r0, int64_t rows) {
+        const int rc = launch_linear(feat + r0 * E, w_logit, b_logit, nullptr, 0.f, 0, rows, S, E, logits, s);
+        return rc ? rc : launch_topk_lse_rows(logits, rows, S, k, ids + r0 * k, logp + r0 * k, lse ? lse + r0 : nullptr, s);
+    });
 }
 
 extern "C" int tal_topk_lse_rows(const float* x, int64_t M, int N, int k, int32_t* ids, float* logp, float* lse, void* stream) {

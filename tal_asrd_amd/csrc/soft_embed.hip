@@ -43,18 +43,6 @@ namespace tal {
 
 namespace {
 
-constexpr int SBM = 128, SBN = 64;
-constexpr int SP_MAX = 16;          // most workgroup slots per row
-constexpr int SHDR = 4;             // floats in front of a partial's out[D]: (max, sum, -, -) -- keeps out[] 16-byte aligned
-
-// rows at and above which auto dispatch takes the fused form.  Rule: the smallest row count of the sweep in profiles/soft_embed.txt
-// from which the fused form measured faster than the generic one at EVERY larger row count of the sweep.  It did at every row count
-// of the ladder, whose smallest is 128 rows (N = 6008; E = 128: fused 0.086 ms, generic 0.112; E = 64: 0.054 / 0.109; at 16,384 rows
-// 0.480 / 4.087 and 0.275 / 3.965; at the 1-hour shape, 44,983 rows, 1.226 / 11.009 and 0.713 / 10.687).  Below 128 rows nothing was
-// measured, so nothing is assumed: the generic form.
-constexpr int64_t FUSED_FROM_ROWS_E64 = 128, FUSED_FROM_ROWS_E128 = 128;
-inline int64_t fused_from_rows(int E) { return E == 64 ? FUSED_FROM_ROWS_E64 : FUSED_FROM_ROWS_E128; }
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int NDB> struct VFrag;
 template <> struct VFrag<4> { typedef f32x4 type; };
@@ -288,48 +276,12 @@ __global__ __launch_bounds__(256) void transpose_values_kernel(const float* __re
     vt[i] = s < N ? values[s * D + d] : 0.f;
 }
 
-// one workgroup per CU by default (the LDS image)
-RunPlan fused_plan(int64_t M, int S) { return head_plan(M, S, SBM, SBN, SP_MAX, 1, device_cus(), opt(OPT_SOFT_EMBED_GRID)); }
-
-size_t fused_ws_bytes(int64_t M, int S, int D) { return (size_t)M * fused_plan(M, S).hp * (size_t)(D + SHDR) * 4; }
-
-int64_t pitch4(int N) { return ((int64_t)N + 3) / 4 * 4; }
-size_t vt_bytes(int N, int D) { return (size_t)D * (size_t)pitch4(N) * 4; }       // (a multiple of 16)
-
-size_t rows_ws_bytes(int64_t M, int N, int D) { return vt_bytes(N, D) + (size_t)generic_chunk_rows(M, pitch4(N)) * (size_t)pitch4(N) * 4; }
-size_t rows_ws_min(int N, int D) { return vt_bytes(N, D) + (size_t)pitch4(N) * 4; }      // (one row of probabilities at least)
-
-bool fused_shape(int E, int D) { return E == D && (E == 64 || E == 128); }
-
-// the form the dispatch takes BY SHAPE under the options in force (alignment is only known at the call)
-bool fused_by_shape(int64_t M, int E, int D) {
-    const int form = opt(OPT_SOFT_EMBED_FORM);
-    return fused_shape(E, D) && (form == 2 || (form == 0 && M >= fused_from_rows(E)));
-}
-
-// What a call is given: the fused form's partials where the dispatch takes it by shape -- and at least the generic form's minimum,
-// so that operands off the 16-byte grid can still run the generic form there, a few rows at a time -- else the generic form's
-// 64 MiB worth of logits (which runs on any workspace that holds values^T and one row).
-size_t soft_embed_ws_bytes(int64_t M, int N, int E, int D) {
-    if (!fused_by_shape(M, E, D)) return rows_ws_bytes(M, N, D);
-    const size_t fused = fused_ws_bytes(M, N, D), least = rows_ws_min(N, D);
-    return fused > least ? fused : least;
-}
-
-bool fused_possible(const float* feat, int64_t ldf, const float* w, const float* values, int E, int D) {
-    return fused_shape(E, D) && ldf % 4 == 0 &&
-           ((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(values)) & 15) == 0;
-}
-
-int launch_soft_embed_fused(const float* feat, int64_t ldf, int E, const float* w, const float* b, const float* values, int64_t M, int S,
-                            float* out, float* lse, void* workspace, hipStream_t s) {
-    const int NT = (int)cdiv(S, SBN);
-    const int64_t U = cdiv(M, SBM) * NT;
-    const RunPlan plan = fused_plan(M, S);
-    const int64_t grid = plan.grid;
-    const int hp = plan.hp;
-    float* part = reinterpret_cast<float*>(workspace);
-    const bool sep = values != w;
+// the fused launch the plan describes
+int launch_soft_embed_fused(const HeadLaunch& p, const float* feat, int64_t ldf, int E, const float* w, const float* b, const float* values,
+                            bool sep, int64_t M, int S, float* out, float* lse, void* workspace, hipStream_t s) {
+    const int NT = p.NT, hp = p.run.hp;
+    const int64_t U = p.U, grid = p.run.grid;
+    float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + p.off[0]);
     {
         ProfScope prof(PROF_GEMM, 4.0 * (double)M * (double)S * E, s);
 #define SOFT_EMBED_LAUNCH(E_, SEP_)                                                                                                  \
@@ -345,7 +297,7 @@ int launch_soft_embed_fused(const float* feat, int64_t ldf, int E, const float* 
 #undef SOFT_EMBED_LAUNCH
         TAL_CHECK_LAUNCH("soft_embed");
     }
-    ProfScope prof(PROF_OTHER, (double)M * hp * (E + SHDR) * 4.0, s);
+    ProfScope prof(PROF_OTHER, (double)p.need, s);
     hipLaunchKernelGGL(soft_embed_merge_kernel, dim3((unsigned)cdiv(M, 4)), dim3(256), 0, s, part, M, E, NT, U, grid, hp, out, lse);
     TAL_CHECK_LAUNCH("soft_embed(merge)");
     return TAL_OK;
@@ -374,40 +326,32 @@ int launch_softmax_matmul(const float* x, int64_t ldx, float* p, int64_t rows, i
     return launch_gemm(g, 0, 1, s);
 }
 
-// tal_soft_embed_fwd behind its argument checks (tal_lm_soft_embed_fwd calls it on the projected rows); values != NULL
-int soft_embed(const char* who, const float* feat, int64_t M, int64_t ldf, int E, const float* w, const float* bias, int N,
+// The entries behind their argument checks (values != NULL): the head on the rows of h [M, ldh] of width E, or on their projection
+// (proj_t != NULL); tal_soft_embed_rows: h = the caller's logits [M, N], no w.  The planned call: the fused launch, or values^T once
+// and then per chunk of rows (as many at a time as the workspace holds, 64 MiB worth at most) the logits through the dense layer (the
+// features' row pitch, the probabilities' padded pitch), probabilities in place -- tal_soft_embed_rows: from the caller's rows --
+// and the dense layer again.
+int soft_embed(int entry, const float* h, int64_t M, int64_t ldh, int E, const float* proj_t, int E0, const float* w, const float* bias, int N,
                const float* values, int D, float* out, float* lse, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    const int form = opt(OPT_SOFT_EMBED_FORM);
-    TAL_CHECK_ARG(form != 2 || fused_possible(feat, ldf, w, values, E, D),
-                  "%s: the fused form needs E == D == 64 or 128, a row pitch that is a multiple of 4 and 16-byte aligned operands "
-                  "(E=%d, D=%d)", who, E, D);
-    const bool fused = fused_by_shape(M, E, D) && fused_possible(feat, ldf, w, values, E, D);
-    const size_t need = fused ? fused_ws_bytes(M, N, D) : rows_ws_min(N, D);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %zu < %zu bytes", who, workspace ? workspace_bytes : (size_t)0, need);
-        return TAL_ENOMEM;
-    }
-    TAL_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
-    if (fused) return launch_soft_embed_fused(feat, ldf, E, w, bias, values, M, N, out, lse, workspace, s);
-    TAL_CHECK_ARG(E % 4 == 0 && ldf % 4 == 0, "%s: the dense layer needs E and the row pitch to be multiples of 4 (E=%d)", who, E);
-    // values^T once, then per chunk of rows: logits through the dense layer (the features' row pitch, the probabilities' padded
-    // pitch), probabilities in place, the dense layer again (as many rows at a time as the workspace holds, 64 MiB worth at most)
-    float* vt = reinterpret_cast<float*>(workspace);
-    float* logits = vt + vt_bytes(N, D) / 4;
-    const int64_t ldp = pitch4(N);
-    int64_t chunk = generic_chunk_rows(M, ldp);
-    const int64_t fit = (int64_t)((workspace_bytes - vt_bytes(N, D)) / ((size_t)ldp * 4));
-    chunk = fit < chunk ? fit : chunk;
-    int rc = launch_transpose_values(values, N, D, vt, s);
-    if (rc) return rc;
-    for (int64_t r0 = 0; r0 < M; r0 += chunk) {
-        const int64_t rows = M - r0 < chunk ? M - r0 : chunk;
-        rc = launch_linear_ld(feat + r0 * ldf, ldf, w, bias, rows, N, E, logits, ldp, s);
-        if (rc) return rc;
-        rc = launch_softmax_matmul(logits, ldp, logits, rows, N, vt, D, out + r0 * D, lse ? lse + r0 : nullptr, s);
-        if (rc) return rc;
-    }
-    return TAL_OK;
+    return head_on_rows(
+        entry, h, M, ldh, E, proj_t, E0, workspace, workspace_bytes, s,
+        [&](const float* feat, int64_t ldf, int width, int proj_in, const void* ws, size_t ws_bytes) {
+            return head_call(entry, M, N, width, D, 1, ldf, proj_in, feat, w, values, ws, ws_bytes);
+        },
+        [&](const HeadCall& c, const HeadLaunch& p, const float* feat, void* ws) {
+            if (p.fused) return launch_soft_embed_fused(p, feat, c.ldf, c.E, w, bias, values, c.sep, M, N, out, lse, ws, s);
+            float* vt = reinterpret_cast<float*>(ws);
+            float* probs = vt + p.vt / 4;
+            const bool have_logits = entry == HE_SOFT_EMBED_ROWS;
+            const int rc = launch_transpose_values(values, N, D, vt, s);
+            return rc ? rc : for_row_chunks(M, p.chunk, [&](int64_t r0, int64_t rows) {
+                const float* x = feat + r0 * c.ldf;
+                const int rcl = have_logits ? TAL_OK : launch_linear_ld(x, c.ldf, w, bias, rows, N, c.E, probs, p.pitch, s);
+                return rcl ? rcl
+                           : launch_softmax_matmul(have_logits ? x : probs, have_logits ? c.ldf : p.pitch, probs, rows, N, vt, D, out + r0 * D,
+                                                   lse ? lse + r0 : nullptr, s);
+            });
+        });
 }
 
 }  // namespace
@@ -417,8 +361,7 @@ int soft_embed(const char* who, const float* feat, int64_t M, int64_t ldf, int E
 using namespace tal;
 
 extern "C" size_t tal_soft_embed_workspace_bytes(int64_t M, int N, int E, int D) {
-    if (M <= 0 || N <= 0 || E <= 0 || D <= 0) return 0;
-    return soft_embed_ws_bytes(M, N, E, D);
+    return head_query_bytes(head_call(HE_SOFT_EMBED, M, N, E, D, 1, E));
 }
 
 extern "C" int tal_soft_embed_fwd(const float* feat, int64_t M, int64_t ldf, int E, const float* w, const float* bias, int N,
@@ -429,13 +372,12 @@ extern "C" int tal_soft_embed_fwd(const float* feat, int64_t M, int64_t ldf, int
     TAL_CHECK_ARG(values || D == E, "tal_soft_embed_fwd: values == NULL (values = w) needs D == E (E=%d, D=%d)", E, D);
     if (M == 0) return TAL_OK;
     TAL_CHECK_ARG(feat && w && out, "tal_soft_embed_fwd: null pointer");
-    return soft_embed("tal_soft_embed_fwd", feat, M, ldf, E, w, bias, N, values ? values : w, D, out, lse, workspace, workspace_bytes,
+    return soft_embed(HE_SOFT_EMBED, feat, M, ldf, E, nullptr, 0, w, bias, N, values ? values : w, D, out, lse, workspace, workspace_bytes,
                       (hipStream_t)stream);
 }
 
 extern "C" size_t tal_soft_embed_rows_workspace_bytes(int64_t M, int N, int D) {
-    if (M <= 0 || N <= 0 || D <= 0) return 0;
-    return rows_ws_bytes(M, N, D);
+    return head_query_bytes(head_call(HE_SOFT_EMBED_ROWS, M, N, D, D, 1, N));
 }
 
 extern "C" int tal_soft_embed_rows(const float* x, int64_t M, int N, const float* values, int D, float* out, float* lse,
@@ -443,32 +385,14 @@ extern "C" int tal_soft_embed_rows(const float* x, int64_t M, int N, const float
     TAL_CHECK_ARG(M >= 0 && N > 0 && D > 0, "tal_soft_embed_rows: bad shape (M=%lld, N=%d, D=%d)", (long long)M, N, D);
     if (M == 0) return TAL_OK;
     TAL_CHECK_ARG(x && values && out, "tal_soft_embed_rows: null pointer");
-    const size_t need = rows_ws_min(N, D);
-    if (!workspace || workspace_bytes < need) {
-        set_error("tal_soft_embed_rows: workspace %zu < %zu bytes", workspace ? workspace_bytes : (size_t)0, need);
-        return TAL_ENOMEM;
-    }
-    TAL_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "tal_soft_embed_rows: the workspace must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    float* vt = reinterpret_cast<float*>(workspace);
-    float* p = vt + vt_bytes(N, D) / 4;
-    const int64_t ldp = pitch4(N);
-    int64_t chunk = generic_chunk_rows(M, ldp);
-    const int64_t fit = (int64_t)((workspace_bytes - vt_bytes(N, D)) / ((size_t)ldp * 4));
-    chunk = fit < chunk ? fit : chunk;
-    int rc = launch_transpose_values(values, N, D, vt, s);
-    if (rc) return rc;
-    for (int64_t r0 = 0; r0 < M; r0 += chunk) {
-        const int64_t rows = M - r0 < chunk ? M - r0 : chunk;
-        rc = launch_softmax_matmul(x + r0 * N, N, p, rows, N, vt, D, out + r0 * D, lse ? lse + r0 : nullptr, s);
-        if (rc) return rc;
-    }
-    return TAL_OK;
+    return soft_embed(HE_SOFT_EMBED_ROWS, x, M, N, D, nullptr, 0, nullptr, nullptr, N, values, D, out, lse, workspace, workspace_bytes,
+                      (hipStream_t)stream);
 }
 
 extern "C" size_t tal_lm_soft_embed_workspace_bytes(int64_t M, int D, int E0, int V, int col_begin) {
-    if (M <= 0 || D <= 0 || E0 <= 0 || V <= 0 || col_begin < 0 || col_begin >= V) return 0;
-    return lm_proj_bytes(M, E0) + soft_embed_ws_bytes(M, V - col_begin, E0, E0);
+    if (D <= 0 || V <= 0 || col_begin < 0 || col_begin >= V) return 0;
+    const size_t head = head_query_bytes(head_call(HE_LM_SOFT_EMBED, M, V - col_begin, E0, E0, 1, E0));
+    return head ? lm_proj_bytes(M, E0) + head : 0;
 }
 
 extern "C" int tal_lm_soft_embed_fwd(const float* h, int64_t M, int64_t ldh, int D, const float* proj_t, int E0, const float* emb, int V,
@@ -478,21 +402,7 @@ extern "C" int tal_lm_soft_embed_fwd(const float* h, int64_t M, int64_t ldh, int
     TAL_CHECK_ARG(proj_t || D == E0, "tal_lm_soft_embed_fwd: no projection needs D == E0");
     if (M == 0) return TAL_OK;
     TAL_CHECK_ARG(h && emb && out, "tal_lm_soft_embed_fwd: null pointer");
-    hipStream_t s = (hipStream_t)stream;
     const float* keys = emb + (int64_t)col_begin * E0;
-    const int N = V - col_begin;
-    if (!proj_t)
-        return soft_embed("tal_lm_soft_embed_fwd", h, M, ldh, D, keys, nullptr, N, keys, E0, out, lse, workspace, workspace_bytes, s);
-    return lm_head_project(
-        "tal_lm_soft_embed_fwd", h, M, ldh, D, proj_t, E0, workspace, workspace_bytes, s,
-        [&](const float* t, size_t& need) -> int {
-            TAL_CHECK_ARG(opt(OPT_SOFT_EMBED_FORM) != 2 || fused_possible(t, E0, keys, keys, E0, E0),
-                          "tal_lm_soft_embed_fwd: the fused form needs E0 == 64 or 128 and 16-byte aligned operands (E0=%d)", E0);
-            TAL_CHECK_ARG(D % 4 == 0 && E0 % 4 == 0, "tal_lm_soft_embed_fwd: D and E0 must be multiples of 4");
-            need = fused_by_shape(M, E0, E0) && fused_possible(t, E0, keys, keys, E0, E0) ? fused_ws_bytes(M, N, E0) : rows_ws_min(N, E0);
-            return TAL_OK;
-        },
-        [&](const float* t, void* ws, size_t ws_bytes) {
-            return soft_embed("tal_lm_soft_embed_fwd", t, M, E0, E0, keys, nullptr, N, keys, E0, out, lse, ws, ws_bytes, s);
-        });
+    return soft_embed(HE_LM_SOFT_EMBED, h, M, ldh, D, proj_t, E0, keys, nullptr, V - col_begin, keys, E0, out, lse, workspace, workspace_bytes,
+                      (hipStream_t)stream);
 }

@@ -19,17 +19,6 @@ namespace tal {
 
 namespace {
 
-// rows at and above which auto dispatch takes the fused form, per feature width.
-// E = 64 (the factorised LM head): the fused form measured faster than the generic one at EVERY row count of the sweep in
-// profiles/lm_xent.txt, whose smallest is 64 rows ((D, E0, V) = (512, 64, 16008): generic 0.119 ms, fused 0.098; (256, 64, 10000):
-// 0.081 / 0.076; at 16,384 rows 2.249 / 0.506 and 1.064 / 0.320).  Below 64 rows nothing was measured, so nothing is assumed.
-// E = 128 (the speaker head): FUSED_FROM_ROWS of csrc/head_topk.hip, the cross-over of the same skeleton at this width
-// (profiles/head_topk.txt).  The sweep of THIS kernel (profiles/lm_xent.txt, last table) puts its own cross-over lower -- 256 rows:
-// generic 0.060 ms, fused 0.076; 512 rows: 0.073 / 0.064 -- so the constant is on the safe side between 512 and 3,750 rows
-// (the generic form there costs up to 0.17 against 0.10 ms at 4,096 rows); lowering it to 512 is a follow-up with its own run.
-constexpr int64_t FUSED_FROM_ROWS_E64 = 64, FUSED_FROM_ROWS_E128 = 3751;
-inline int64_t fused_from_rows(int E) { return E == 64 ? FUSED_FROM_ROWS_E64 : FUSED_FROM_ROWS_E128; }
-
 // the column a target can match: -1 (no column) for a skipped row and for a target past the head
 __device__ __forceinline__ int target_col(int64_t t, int N) { return t >= 0 && t < (int64_t)N ? (int)t : -1; }
 
@@ -141,31 +130,6 @@ __global__ __launch_bounds__(256) void xent_lse_rows_kernel(const float* __restr
     wave_finish(mx, sm, bv, bi, tz, tgt, row, lane, nll, lse, top1);
 }
 
-// two workgroups per CU by default
-RunPlan xent_plan(int64_t M, int S) { return head_plan(M, S, HS_BM, HS_BN, HS_SLOTS, 2, device_cus(), opt(OPT_XENT_GRID)); }
-
-// per row, slot and lane half: (max, sum, best value, target logit) and the best index
-size_t fused_ws_bytes(int64_t M, int S) { return (size_t)M * xent_plan(M, S).hp * 2 * 20; }
-
-size_t generic_ws_bytes(int64_t M, int S) { return (size_t)generic_chunk_rows(M, S) * (size_t)S * 4; }
-
-bool fused_shape(int E) { return E == 64 || E == 128; }
-
-// the form the dispatch takes BY SHAPE under the options in force (alignment is only known at the call)
-bool fused_by_shape(int64_t M, int E) {
-    const int form = opt(OPT_XENT_FORM);
-    return fused_shape(E) && (form == 2 || (form == 0 && M >= fused_from_rows(E)));
-}
-
-// What a call is given: the fused form's partials where the dispatch takes it by shape -- and at least one row of logits, so that
-// operands off the 16-byte grid can still run the generic form there, a few rows at a time -- else 64 MiB worth of the generic
-// form's logits (which runs on any workspace that holds one row).
-size_t xent_rows_ws_bytes(int64_t M, int N, int E) {
-    if (!fused_by_shape(M, E)) return generic_ws_bytes(M, N);
-    const size_t fused = fused_ws_bytes(M, N), row = (size_t)N * 4;
-    return fused > row ? fused : row;
-}
-
 int launch_xent_lse_rows(const float* x, int64_t M, int N, const int64_t* target, float* nll, float* lse, int32_t* top1, hipStream_t s) {
     ProfScope prof(PROF_OTHER, (double)M * N * 4.0, s);
     hipLaunchKernelGGL(xent_lse_rows_kernel, dim3((unsigned)cdiv(M, 4)), dim3(256), 0, s, x, M, N, target, nll, lse, top1);
@@ -173,15 +137,13 @@ int launch_xent_lse_rows(const float* x, int64_t M, int N, const int64_t* target
     return TAL_OK;
 }
 
-int launch_xent_fused(const float* feat, int64_t ldf, int E, const float* w, const float* b, const int64_t* target, int64_t M, int S,
-                      float* nll, float* lse, int32_t* top1, void* workspace, hipStream_t s) {
-    const int NT = (int)cdiv(S, HS_BN);
-    const int64_t U = cdiv(M, HS_BM) * NT;
-    const RunPlan plan = xent_plan(M, S);
-    const int64_t grid = plan.grid;
-    const int hp = plan.hp;
-    float* pf = reinterpret_cast<float*>(workspace);
-    int32_t* pi = reinterpret_cast<int32_t*>(pf + (size_t)M * hp * 2 * 4);
+// the fused launch the plan describes
+int launch_xent_fused(const HeadLaunch& p, const float* feat, int64_t ldf, int E, const float* w, const float* b, const int64_t* target,
+                      int64_t M, int S, float* nll, float* lse, int32_t* top1, void* workspace, hipStream_t s) {
+    const int NT = p.NT, hp = p.run.hp;
+    const int64_t U = p.U, grid = p.run.grid;
+    float* pf = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + p.off[0]);
+    int32_t* pi = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + p.off[1]);
     {
         ProfScope prof(PROF_GEMM, 2.0 * (double)M * (double)S * E, s);
         const XentScan::Args args = {target, pf, pi};
@@ -191,46 +153,32 @@ int launch_xent_fused(const float* feat, int64_t ldf, int E, const float* w, con
             hipLaunchKernelGGL((head_stream_kernel<128, XentScan>), dim3((unsigned)grid), dim3(256), 0, s, feat, ldf, w, b, M, S, NT, U, args, hp);
         TAL_CHECK_LAUNCH("xent");
     }
-    ProfScope prof(PROF_OTHER, (double)M * hp * 2 * 20.0, s);
+    ProfScope prof(PROF_OTHER, (double)p.need, s);
     hipLaunchKernelGGL(xent_merge_kernel, dim3((unsigned)cdiv(M, 4)), dim3(256), 0, s, pf, pi, target, M, NT, U, grid, hp, nll, lse, top1);
     TAL_CHECK_LAUNCH("xent(merge)");
     return TAL_OK;
 }
 
-bool fused_possible(const float* feat, int64_t ldf, const float* w, int E) {
-    return fused_shape(E) && ldf % 4 == 0 && ((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(w)) & 15) == 0;
-}
-
-// tal_xent_rows_fwd behind its argument checks (tal_lm_xent_fwd calls it on the projected rows)
-int xent_rows(const char* who, const float* feat, int64_t M, int64_t ldf, int E, const float* w, const float* bias, int N,
+// tal_xent_rows_fwd and tal_lm_xent_fwd behind their argument checks: the head on the rows of h, or on their projection (proj_t != NULL).
+// The planned call: the fused launch, or the logits of a chunk of rows through the dense layer (launch_linear's launch, with the
+// features' row pitch), then the row kernel (as many rows at a time as the workspace holds, 64 MiB worth at most:
+// tal_xent_rows_workspace_bytes asks for that much where it expects this form; a smaller workspace means more, shorter launches)
+int xent_rows(int entry, const float* h, int64_t M, int64_t ldh, int D, const float* proj_t, int E0, const float* w, const float* bias, int N,
               const int64_t* target, float* nll, float* lse, int32_t* top1, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    const int form = opt(OPT_XENT_FORM);
-    TAL_CHECK_ARG(form != 2 || fused_possible(feat, ldf, w, E),
-                  "%s: the fused form needs E == 64 or 128, a row pitch that is a multiple of 4 and 16-byte aligned operands (E=%d)", who, E);
-    const bool fused = fused_by_shape(M, E) && fused_possible(feat, ldf, w, E);
-    const size_t need = fused ? fused_ws_bytes(M, N) : (size_t)N * 4;        // (generic: one row of logits at least)
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %zu < %zu bytes", who, workspace ? workspace_bytes : (size_t)0, need);
-        return TAL_ENOMEM;
-    }
-    TAL_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
-    if (fused) return launch_xent_fused(feat, ldf, E, w, bias, target, M, N, nll, lse, top1, workspace, s);
-    // the logits of a chunk of rows through the dense layer (launch_linear's launch, with the features' row pitch), then the row kernel
-    // (as many rows at a time as the workspace holds, 64 MiB worth at most: tal_xent_rows_workspace_bytes asks for that much where
-    //  it expects this form; a smaller workspace means more, shorter launches)
-    int64_t chunk = generic_chunk_rows(M, N);
-    const int64_t fit = (int64_t)(workspace_bytes / ((size_t)N * 4));
-    chunk = fit < chunk ? fit : chunk;
-    float* logits = reinterpret_cast<float*>(workspace);
-    for (int64_t r0 = 0; r0 < M; r0 += chunk) {
-        const int64_t rows = M - r0 < chunk ? M - r0 : chunk;
-        int rc = ldf == E ? launch_linear(feat + r0 * ldf, w, bias, nullptr, 0.f, 0, rows, N, E, logits, s)
-                          : launch_linear_ld(feat + r0 * ldf, ldf, w, bias, rows, N, E, logits, N, s);
-        if (rc) return rc;
-        rc = launch_xent_lse_rows(logits, rows, N, target + r0, nll + r0, lse ? lse + r0 : nullptr, top1 ? top1 + r0 : nullptr, s);
-        if (rc) return rc;
-    }
-    return TAL_OK;
+    return head_on_rows(
+        entry, h, M, ldh, D, proj_t, E0, workspace, workspace_bytes, s,
+        [&](const float* feat, int64_t ldf, int E, int proj_in, const void* ws, size_t ws_bytes) {
+            return head_call(entry, M, N, E, E, 1, ldf, proj_in, feat, w, w, ws, ws_bytes);
+        },
+        [&](const HeadCall& c, const HeadLaunch& p, const float* feat, void* ws) {
+            if (p.fused) return launch_xent_fused(p, feat, c.ldf, c.E, w, bias, target, M, N, nll, lse, top1, ws, s);
+            float* logits = reinterpret_cast<float*>(ws);
+            return for_row_chunks(M, p.chunk, [&](int64_t r0, int64_t rows) {
+                const int rc = c.ldf == c.E ? launch_linear(feat + r0 * c.ldf, w, bias, nullptr, 0.f, 0, rows, N, c.E, logits, s)
+                                            : launch_linear_ld(feat + r0 * c.ldf, c.ldf, w, bias, rows, N, c.E, logits, N, s);
+                return rc ? rc : launch_xent_lse_rows(logits, rows, N, target + r0, nll + r0, lse ? lse + r0 : nullptr, top1 ? top1 + r0 : nullptr, s);
+            });
+        });
 }
 
 }  // namespace
@@ -239,10 +187,7 @@ int xent_rows(const char* who, const float* feat, int64_t M, int64_t ldf, int E,
 
 using namespace tal;
 
-extern "C" size_t tal_xent_rows_workspace_bytes(int64_t M, int N, int E) {
-    if (M <= 0 || N <= 0 || E <= 0) return 0;
-    return xent_rows_ws_bytes(M, N, E);
-}
+extern "C" size_t tal_xent_rows_workspace_bytes(int64_t M, int N, int E) { return head_query_bytes(head_call(HE_XENT_ROWS, M, N, E, E, 1, E)); }
 
 extern "C" int tal_xent_rows_fwd(const float* feat, int64_t M, int64_t ldf, int E, const float* w, const float* bias, int N,
                                  const int64_t* target, float* nll, float* lse, int32_t* top1, void* workspace,
@@ -251,8 +196,7 @@ extern "C" int tal_xent_rows_fwd(const float* feat, int64_t M, int64_t ldf, int 
                   (long long)ldf, E, N);
     if (M == 0) return TAL_OK;
     TAL_CHECK_ARG(feat && w && target && nll, "tal_xent_rows_fwd: null pointer");
-    return xent_rows("tal_xent_rows_fwd", feat, M, ldf, E, w, bias, N, target, nll, lse, top1, workspace, workspace_bytes,
-                     (hipStream_t)stream);
+    return xent_rows(HE_XENT_ROWS, feat, M, ldf, E, nullptr, 0, w, bias, N, target, nll, lse, top1, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int tal_xent_lse_rows(const float* x, int64_t M, int N, const int64_t* target, float* nll, float* lse, int32_t* top1,
@@ -264,8 +208,9 @@ extern "C" int tal_xent_lse_rows(const float* x, int64_t M, int N, const int64_t
 }
 
 extern "C" size_t tal_lm_xent_workspace_bytes(int64_t M, int D, int E0, int V) {
-    if (M <= 0 || D <= 0 || E0 <= 0 || V <= 0) return 0;
-    return lm_proj_bytes(M, E0) + xent_rows_ws_bytes(M, V, E0);
+    if (D <= 0) return 0;
+    const size_t head = head_query_bytes(head_call(HE_LM_XENT, M, V, E0, E0, 1, E0));
+    return head ? lm_proj_bytes(M, E0) + head : 0;
 }
 
 extern "C" int tal_lm_xent_fwd(const float* h, int64_t M, int64_t ldh, int D, const float* proj_t, int E0, const float* emb, int V,
@@ -275,18 +220,5 @@ extern "C" int tal_lm_xent_fwd(const float* h, int64_t M, int64_t ldh, int D, co
     TAL_CHECK_ARG(proj_t || D == E0, "tal_lm_xent_fwd: no projection needs D == E0");
     if (M == 0) return TAL_OK;
     TAL_CHECK_ARG(h && emb && target && nll, "tal_lm_xent_fwd: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    if (!proj_t)
-        return xent_rows("tal_lm_xent_fwd", h, M, ldh, D, emb, nullptr, V, target, nll, lse, top1, workspace, workspace_bytes, s);
-    return lm_head_project(
-        "tal_lm_xent_fwd", h, M, ldh, D, proj_t, E0, workspace, workspace_bytes, s,
-        [&](const float* t, size_t& need) -> int {
-            TAL_CHECK_ARG(opt(OPT_XENT_FORM) != 2 || fused_possible(t, E0, emb, E0),
-                          "tal_lm_xent_fwd: the fused form needs E0 == 64 or 128 and 16-byte aligned operands (E0=%d)", E0);
-            need = fused_by_shape(M, E0) && fused_possible(t, E0, emb, E0) ? fused_ws_bytes(M, V) : (size_t)V * 4;
-            return TAL_OK;
-        },
-        [&](const float* t, void* ws, size_t ws_bytes) {
-            return xent_rows("tal_lm_xent_fwd", t, M, E0, E0, emb, nullptr, V, target, nll, lse, top1, ws, ws_bytes, s);
-        });
+    return xent_rows(HE_LM_XENT, h, M, ldh, D, proj_t, E0, emb, nullptr, V, target, nll, lse, top1, workspace, workspace_bytes, (hipStream_t)stream);
 }
